@@ -14,16 +14,22 @@ Launch: `python bench.py --gpus N` starts N rank processes itself (one per GPU, 
 it is not already running under torch.distributed.run; the parent never touches the GPU, polls its
 children and terminates the others as soon as one fails.
 
-Prints ONE JSON line on rank 0 (driver contract) with
+A plain run (`python bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints
+ONE JSON line on rank 0 (driver contract) with the headline (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = wall milliseconds per timed step) and
   * `roofline`: MFMA-bound; algorithmic flops per launch / HIP-event-timed average launch, against the
     matrix pipe the kernel runs on (fp16 for fp32x3 -- `executed_frac` counts its three products);
+  * `dist`: the world size torch.distributed reports after init and every rank's device (PCI bus id).
+--dump-outputs DIR also writes the last timed step's samples, (1, chains_total, 3) float32, to DIR/samples.npy
+(y, weights and the per-step seeds depend on the arguments alone: two builds can be compared sample for sample).
+With --full the run goes on after the headline and adds to the line
   * `cpu_baseline`: reference-order torch-CPU sampler on a bounded sample (rank 0, N = 1 only);
   * `ks_vs_ref` / `w1_vs_ref` / `parity`: the timed run's samples against the reference sampler's own
     draws (tests/golden/samples_scat.npz: 20k draws and the 1001 quantiles of its 100k-chain run, same
     y and weights): per-dimension KS (alpha = 0.01), per-dimension and sliced W1 with their null levels;
   * `fast_mode`: the same workload on the 16-bit engine (fp16 hidden layers), `fp32_mode`: on the
     exact-f32 engine (v_mfma_f32_16x16x4_f32) -- each timed after the headline with its own parity report;
-  * `dist`: the world size torch.distributed reports after init and every rank's device (PCI bus id).
+  * `other_configs`: BASELINE configs 1 and 3-5 and the reference width [512]*3 on this GPU (N = 1 only).
 Other workloads (not the headline): --workload cdiffe-pc (BASELINE config 3: CDiffE + 1 Langevin
 corrector step, --chains-total 1000000 sharded over the ranks: strong scaling) and --workload dps
 (config 4: DPS with surrogate guidance, --chains-total 262144; fp32x3 by default, --precision fp32 for the
@@ -100,6 +106,12 @@ def parse():
                     help="seconds before a blocked collective (a dead rank) fails the job")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the one-GPU runs of BASELINE configs 3-5 and the reference width reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the line can report: parity against the reference's "
+                         "draws, the 16-bit and exact-f32 engines, BASELINE configs 3-5 and the reference width, the CPU "
+                         "baseline (each can be dropped again with its --no-* option); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32)")
     ap.add_argument("--master-port", type=int, default=29511)
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)  # CPU/gloo launcher test only
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)  # launcher fail-fast test
@@ -387,6 +399,26 @@ def timed(wl, steps, dist, world, dev, seed0=0, **over):
     return elapsed, launch_ms, x
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array of `arrays` (name -> tensor, what the last timed step returned to its caller) as
+    out_dir/<name>.npy in float32 (float64 stays float64). The inputs (y, weights, per-step seeds) are functions of
+    the arguments alone, so two builds run with the same arguments can be compared array for array. An output over
+    its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its rows (in row order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, x in arrays.items():
+        a = x.detach().cpu().numpy()
+        a = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+        if a.nbytes > budget:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = budget // (rows.shape[1] * a.itemsize)
+            a = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def other_configs(args, pkg, lib, dev):
     """The other BASELINE configurations on this GPU, timed beside the headline so the driver observes
     them (each: one warm-up launch, then timed launches with HIP events): configs[2] CDiffE
@@ -594,6 +626,8 @@ def main_worker(args):
     elapsed, launch_ms, x_last = timed(wl, args.steps, dist, world, dev)
     if not args.stub:
         lib.device_status(dev)  # no asynchronous kernel failure in the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"samples": x_last})
 
     ms_per_step = elapsed / args.steps * 1e3
     value = wl.n_total * args.steps / elapsed
@@ -639,19 +673,20 @@ def main_worker(args):
         if world > 1:
             dist.destroy_process_group()
         return 0 if line["stub"]["gather_ok"] else 1
-    rep = None
-    if args.workload == "cde" and rank == 0:
+    # everything below is beside the headline: only with --full
+    extras = args.full and args.workload == "cde"
+    if extras and rank == 0:
         rep = parity_vs_reference(metrics, x_last.reshape(-1, XDIM).cpu().numpy(), S, wl.weights)
         line["ks_vs_ref"] = ks_field(rep)
         line["w1_vs_ref"] = w1_field(rep)
         line["parity"] = {"pass": rep["pass"]} if rep else None
-    if args.workload == "cde" and prec != "fp16" and not args.no_fast:
+    if extras and prec != "fp16" and not args.no_fast:
         line["fast_mode"] = side_mode(wl, args, dist, world, dev, lib, metrics, "fp16", args.fast_steps, S, flops_launch)
-    if args.workload == "cde" and prec != "fp32" and not args.no_fp32:
+    if extras and prec != "fp32" and not args.no_fp32:
         line["fp32_mode"] = side_mode(wl, args, dist, world, dev, lib, metrics, "fp32", args.fp32_steps, S, flops_launch)
-    if rank == 0 and world == 1 and args.workload == "cde" and not args.no_other_configs:
+    if extras and rank == 0 and world == 1 and not args.no_other_configs:
         line["other_configs"] = other_configs(args, pkg, lib, dev)
-    if rank == 0 and world == 1 and args.workload == "cde" and not args.no_cpu_baseline:
+    if extras and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(S, args.cpu_chains)
     if rank == 0:
         print(json.dumps(line), flush=True)

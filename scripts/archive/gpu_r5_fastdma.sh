@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 500 python -u -m pytest -x -q --timeout 200 --timeout-method thread tests/test_gpu_parity.py > "$OUT/pytest.log" 2>&1 || { tail -30 "$OUT/pytest.log"; exit 3; }
 tail -1 "$OUT/pytest.log"
-B=(python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-other-configs)
+B=(python -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-other-configs)
 for r in 1 2; do
   for lib in new base; do
     if [ $lib = base ]; then export DMIP_LIB=$BASE DMIP_LIB_AB=1; else unset DMIP_LIB DMIP_LIB_AB; fi

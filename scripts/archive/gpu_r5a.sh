@@ -26,6 +26,6 @@ done
 P=(python scripts/bench_config5.py --steps 5)
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_CYCLES_VMEM SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_WAIT_INST_LDS -d "$OUT/pmc_2" -o pmc --output-format csv -- "${P[@]}" > "$OUT/p2.log" 2>&1 || exit 3
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS -d "$OUT/pmc_1" -o pmc --output-format csv -- "${P[@]}" > "$OUT/p1.log" 2>&1 || exit 3
-timeout -k 10 600 python -u bench.py --steps 10 --warmup 3 > "$OUT/bench.log" 2>&1 || { tail -5 "$OUT/bench.log"; exit 3; }
+timeout -k 10 600 python -u bench.py --full --steps 10 --warmup 3 > "$OUT/bench.log" 2>&1 || { tail -5 "$OUT/bench.log"; exit 3; }
 tail -1 "$OUT/bench.log" | cut -c1-400
 echo done

@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_x3k.py tests/test_gpu_x3.py
   -m gpu -k "x3 or corrector" -v -s --timeout 120 --timeout-method thread -p no:cacheprovider > "$OUT/pytest.log" 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "FAILED|Error|passed|failed|\[x3k\]" "$OUT/pytest.log" | tail -30
 case $rc in 0|1) ;; *) exit $rc ;; esac
-B=(python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-fast --no-other-configs)
+B=(python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-fast --no-other-configs)
 run() {  # run <name> <env...>
   local n=$1; shift
   env "$@" timeout -k 10 300 "${B[@]}" > "$OUT/bench_$n.log" 2>&1 || { echo "bench $n failed"; tail -5 "$OUT/bench_$n.log"; exit 3; }

@@ -9,7 +9,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_x3k.py -m gpu -v -s --timeo
   -p no:cacheprovider > "$OUT/pytest.log" 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "FAILED|Error|passed|failed" "$OUT/pytest.log" | tail -8
 case $rc in 0|1) ;; *) exit $rc ;; esac
-B=(python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-fast --no-other-configs)
+B=(python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-fast --no-other-configs)
 run() {  # run <name> <env...>
   local n=$1; shift
   env "$@" timeout -k 10 300 "${B[@]}" > "$OUT/bench_$n.log" 2>&1 || { echo "bench $n failed"; tail -5 "$OUT/bench_$n.log"; exit 3; }

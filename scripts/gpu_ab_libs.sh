@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-ablibs}
 shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
-B=(python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-fast --no-other-configs)
+B=(python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-fp32 --no-fast --no-other-configs)
 for r in 1 2; do
   for lib in default "$@"; do
     n=$(basename "$lib" .so)_$r

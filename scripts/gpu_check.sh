@@ -26,9 +26,9 @@ step() {  # step <name> <seconds> <cmd...>
 
 step pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread -p no:cacheprovider -rf
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python -u bench.py --steps 10 --warmup 3
+step bench 600 python -u bench.py --full --steps 10 --warmup 3
 cd /tmp && mkdir -p prof && cd - > /dev/null
 step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+  python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 find "$OUT/prof" -name "*stats*" -exec cp {} "$OUT/" \; 2>/dev/null
 echo "done" | tee -a "$OUT/steps.log"

@@ -8,7 +8,7 @@ shift || true
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH=(python bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@")
+BENCH=(python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@")
 
 rocprofv3 -L > "$OUT/counters_list.txt" 2>&1 || true
 

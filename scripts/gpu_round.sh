@@ -20,11 +20,11 @@ step() {  # step <name> <seconds> <cmd...>
 }
 step pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread -p no:cacheprovider -rf
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python -u bench.py --steps 10 --warmup 3
+step bench 600 python -u bench.py --full --steps 10 --warmup 3
 step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python bench.py --steps 5 --warmup 2 --no-cpu-baseline
+  python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
 find "$OUT/prof" -name "*kernel_stats*" -exec cp {} "$OUT/kernel_stats.csv" \; 2>/dev/null
-PB=(python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --fast-steps 2 --fp32-steps 1)
+PB=(python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --fast-steps 2 --fp32-steps 1)
 step pmc_fetch 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o pmc --output-format csv -- "${PB[@]}"
 step pmc_write 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o pmc --output-format csv -- "${PB[@]}"
 python scripts/pmc_traffic.py "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/pmc_traffic.json"

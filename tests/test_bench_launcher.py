@@ -72,6 +72,41 @@ def test_config4_dps_strong_scaling_line():
     assert out["stub"]["gather_ok"] and out["config"]["chains_per_gpu"] == 5
 
 
+def test_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain run reports the headline fields and none of the --full extras; --dump-outputs writes what the last
+    timed step returned (seed = steps - 1 in the stand-in's column 1), identical from run to run."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        line = _run(["--gpus", "1", "--chains", "37", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "samples/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "fp32" and "posterior samples/sec" in line["metric"]
+        assert abs(line["value"] - 37 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert not {"ks_vs_ref", "w1_vs_ref", "parity", "fast_mode", "fp32_mode", "other_configs", "cpu_baseline"} & set(line)
+        assert os.listdir(tmp_path / d) == ["samples.npy"]
+        outs.append(np.load(tmp_path / d / "samples.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (1, 37, 3)
+    assert np.array_equal(outs[0][0, :, 0], np.arange(37)) and np.all(outs[0][0, :, 1] == 2.0)
+    assert np.array_equal(outs[0], outs[1])
+
+
+def test_dump_outputs_caps_a_large_output_with_a_fixed_sample(tmp_path, monkeypatch):
+    import importlib
+    import numpy as np
+    import torch
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 100 * 3 * 4)
+    x = torch.arange(2 * 500 * 3, dtype=torch.float64).reshape(2, 500, 3)
+    small = torch.ones(1, 10, 3, dtype=torch.float16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "small": small})
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float64 and a.shape == (50, 3) and np.array_equal(a, b)  # 1200 of the 2400 bytes each
+    assert np.all(np.diff(a[:, 0]) > 0) and np.array_equal(a[:, 1], a[:, 0] + 1)  # whole rows of x, in order
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (1, 10, 3)
+
+
 def test_mismatched_world_size_is_an_error():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--gpus", "2"],
