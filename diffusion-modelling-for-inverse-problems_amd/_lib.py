@@ -39,7 +39,7 @@ EXPORTED = (
     "dmip_sampler_supported_f32", "dmip_posterior_loss_grad", "dmip_loss_grad_f32", "dmip_train_draws",
     "dmip_adam_step", "dmip_em_sample_snapshots", "dmip_train_plan_create", "dmip_train_plan_step",
     "dmip_train_plan_set_counters", "dmip_train_plan_destroy", "dmip_sampler_supported_precision",
-    "dmip_dps_sample_ex", "dmip_mh_sample_ex",
+    "dmip_dps_sample_ex", "dmip_mh_sample_ex", "dmip_em_sample_lmbd", "dmip_flow_logp", "dmip_flow_logp_supported",
 )
 DMIP_DPS_NLL, DMIP_DPS_NORM = 0, 1
 
@@ -122,6 +122,16 @@ def _declare(lib):
         lib.dmip_em_sample_snapshots.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32,
                                                  _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _i32, _f32,
                                                  _i32, _c_void_p, _c_void_p, _c_void_p]
+    if hasattr(lib, "dmip_em_sample_lmbd"):  # (absent from older builds loaded by A/B timing scripts)
+        lib.dmip_em_sample_lmbd.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32,
+                                            _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, ctypes.c_double, _c_void_p,
+                                            _i32, _c_void_p, _c_void_p, _c_void_p]
+        lib.dmip_em_sample_lmbd.restype = _i32
+        lib.dmip_flow_logp.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p, _i32,
+                                       _i32, _i32, _i64, _i32, _c_void_p, _c_void_p, _c_void_p]
+        lib.dmip_flow_logp.restype = _i32
+        lib.dmip_flow_logp_supported.argtypes = [_i32, _i32, _i32, _i32, _i32]
+        lib.dmip_flow_logp_supported.restype = _i32
     if hasattr(lib, "dmip_train_plan_create"):
         lib.dmip_train_plan_create.argtypes = [ctypes.POINTER(DmipTrainPlanDesc), ctypes.POINTER(_c_void_p)]
         lib.dmip_train_plan_step.argtypes = [_c_void_p, _c_void_p, _c_void_p, _c_void_p]
@@ -335,6 +345,34 @@ def em_sample_snapshots(mode, net, prior, sde, y, n_chains, chain_offset, num_st
                                          ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), precision_code(precision),
                                          int(corrector_steps), float(snr), int(snapshot_every), ptr(snaps), ptr(out),
                                          stream_of(y.device)))
+
+
+def em_sample_lmbd(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, lmbd, out, noise=None,
+                   snapshot_every=0, snaps=None, precision="fp16"):
+    """dmip_em_sample_lmbd: the fused CDE / Posterior sampler of the lambda family (sdes.py:77-87; lmbd = 1 the
+    probability-flow ODE), optionally with trajectory snapshots."""
+    calls["em_sample_lmbd"] = calls.get("em_sample_lmbd", 0) + 1
+    _status_pending.add(_dev_index(y.device))
+    n_y, ydim = y.shape
+    check(lib().dmip_em_sample_lmbd(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde), ptr(y),
+                                    n_y, ydim, net.xdim, int(n_chains), int(chain_offset), int(num_steps), float(mean),
+                                    float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                    precision_code(precision), float(lmbd), ptr(noise), int(snapshot_every), ptr(snaps),
+                                    ptr(out), stream_of(y.device)))
+
+
+def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE):
+    return bool(lib().dmip_flow_logp_supported(mode, width, n_hidden, xdim, ydim))
+
+
+def flow_logp(mode, net, prior, sde, x, y, num_steps, logp, latent=None):
+    """dmip_flow_logp: log p(x | y) of x (n_y, n, xdim) under ys (n_y, ydim) into logp (n_y, n) [and x_S into latent]."""
+    calls["flow_logp"] = calls.get("flow_logp", 0) + 1
+    _status_pending.add(_dev_index(y.device))  # (parallel.guarded then reads the status word after the launch)
+    n_y, ydim = y.shape
+    check(lib().dmip_flow_logp(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde), ptr(x),
+                               ptr(y), n_y, ydim, net.xdim, int(x.shape[1]), int(num_steps), ptr(logp), ptr(latent),
+                               stream_of(y.device)))
 
 
 def sampler_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp16"):

@@ -944,7 +944,15 @@ struct SampleArgs {
   float snr = 0.16f;
   int snap_every = 0;
   float* snap_out_dev = nullptr;
+  double lmbd = 0.0;  // sdes.py:77-87: 0 the reverse SDE, 1 the probability-flow ODE (CDE and Posterior)
 };
+
+// step_coef's lambda factors: the Python scalars (1 - 0.5 lmbd) and (1 - lmbd) ** 0.5, evaluated in double and rounded
+// once to the f32 torch multiplies the tensor g by (exactly 1, 1 at lmbd = 0)
+static void lmbd_factors(const SampleArgs& a, float& c_mu, float& c_sig) {
+  c_mu = (float)(1.0 - 0.5 * a.lmbd);
+  c_sig = (float)std::sqrt(1.0 - a.lmbd);
+}
 
 static void fill_schedule(const SampleArgs& a, float& T, float& bmin, float& bdiff, float& delta, float& sqrt_delta) {
   T = (float)a.sde->T;
@@ -991,6 +999,7 @@ static int em_sample_f32(int mode, const dmip_mlp* net0, const dmip_mlp* net1, c
   p.chain_offset = a.chain_offset;
   p.num_steps = a.num_steps;
   fill_schedule(a, p.T, p.bmin, p.bdiff, p.delta, p.sqrt_delta);
+  lmbd_factors(a, p.c_mu, p.c_sig);
   p.mean = a.mean;
   p.stdv = a.stdv;
   p.seed = a.seed;
@@ -1074,6 +1083,7 @@ static int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, co
   p.chain_offset = a.chain_offset;
   p.num_steps = a.num_steps;
   fill_schedule(a, p.T, p.bmin, p.bdiff, p.delta, p.sqrt_delta);
+  lmbd_factors(a, p.c_mu, p.c_sig);
   p.mean = a.mean;
   p.stdv = a.stdv;
   p.seed = a.seed;
@@ -1134,6 +1144,9 @@ static int em_sample_impl(int mode, const dmip_mlp* net0, const dmip_mlp* net1, 
   if (a.n_chains < 0 || a.chain_offset < 0) return fail(DMIP_ERR_INVALID, "negative chain count/offset");
   if (a.num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
   if (!(a.sde->T > 0.0)) return fail(DMIP_ERR_INVALID, "T must be > 0");
+  if (!(a.lmbd >= 0.0 && a.lmbd <= 1.0)) return fail(DMIP_ERR_INVALID, "lmbd must be in [0, 1]");
+  if (a.lmbd != 0.0 && mode == DMIP_SAMPLER_CDIFFE)
+    return fail(DMIP_ERR_INVALID, "lmbd != 0: CDE and Posterior samplers only");
   if (f32_act(net0) || (net1 && f32_act(net1))) {
     if (a.precision != DMIP_PREC_F32 || mode != DMIP_SAMPLER_CDE) return act_refused("em_sample");
   }
@@ -1209,6 +1222,7 @@ static int em_sample_impl(int mode, const dmip_mlp* net0, const dmip_mlp* net1, 
   p.bdiff = (float)(a.sde->beta_max - a.sde->beta_min);
   p.delta = (float)(a.sde->T / (double)a.num_steps);
   p.sqrt_delta = (float)std::sqrt(a.sde->T / (double)a.num_steps);
+  lmbd_factors(a, p.c_mu, p.c_sig);
   p.mean = a.mean;
   p.stdv = a.stdv;
   p.seed = a.seed;
@@ -1279,6 +1293,91 @@ int dmip_em_sample_snapshots(int mode, const dmip_mlp* net, const dmip_mlp* prio
   a.snap_every = snapshot_every;
   a.snap_out_dev = snap_out_dev;
   return em_sample_impl(mode, net, mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr, a);
+}
+
+int dmip_em_sample_lmbd(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                        int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                        float stdv, uint64_t seed, int precision, double lmbd, const float* noise_dev,
+                        int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "em_sample_lmbd: CDE and Posterior samplers only");
+  if (mode == DMIP_SAMPLER_POSTERIOR && !prior) return fail(DMIP_ERR_INVALID, "null argument");
+  if (!(lmbd >= 0.0 && lmbd <= 1.0)) return fail(DMIP_ERR_INVALID, "lmbd must be in [0, 1]");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (snapshot_every < 0 || (snapshot_every > 0 && (snapshot_every > num_steps || !snap_out_dev)))
+    return fail(DMIP_ERR_INVALID, "snapshot_every must be 0 or in [1, num_steps] with a snapshot buffer");
+  SampleArgs a{sde,  y_dev, n_y,       ydim,      xdim,      n_chains, chain_offset, num_steps,
+               mean, stdv,  seed,      precision, noise_dev, x_out_dev, stream,      nullptr};
+  a.snap_every = snapshot_every;
+  a.snap_out_dev = snapshot_every > 0 ? snap_out_dev : nullptr;
+  a.lmbd = lmbd;
+  return em_sample_impl(mode, net, mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr, a);
+}
+
+int dmip_flow_logp_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
+  return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+}
+
+// log p(x | y) along the probability-flow ODE (dmip_flow.hip); every argument is validated before any device work
+int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
+                   const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
+                   float* latent_out_dev, void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "flow_logp: CDE and Posterior estimators only");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (!net || !sde || !x_dev || !y_dev || !logp_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
+    return fail(DMIP_ERR_INVALID, "null argument");
+  if (net->layout != DMIP_INPUT_X_Y_T) return fail(DMIP_ERR_INVALID, "flow_logp needs an x,y,t network");
+  if (xdim != net->xdim || net->out_dim != xdim) return fail(DMIP_ERR_INVALID, "xdim does not match the network");
+  if (ydim != net->in_dim - xdim - 1) return fail(DMIP_ERR_INVALID, "ydim does not match the network");
+  if (mode == DMIP_SAMPLER_POSTERIOR) {
+    if (prior->layout != DMIP_INPUT_X_T || prior->xdim != xdim || prior->out_dim != xdim)
+      return fail(DMIP_ERR_INVALID, "prior must be an x,t network with out_dim == xdim");
+    if (prior->width != net->width || prior->n_hidden != net->n_hidden)
+      return fail(DMIP_ERR_UNSUPPORTED, "prior and likelihood networks must have the same hidden layers");
+  }
+  if (n_y < 1 || n_y > 65535) return fail(DMIP_ERR_INVALID, "n_y must be in [1, 65535]");
+  if (n < 0) return fail(DMIP_ERR_INVALID, "negative row count");
+  if (!(sde->T > 0.0)) return fail(DMIP_ERR_INVALID, "T must be > 0");
+  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
+  if (f32_act(net) || (net1 && f32_act(net1)))
+    return fail(DMIP_ERR_UNSUPPORTED, "flow_logp: the tanh chain only (no SiLU log-likelihood kernel)");
+  if (!dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim))
+    return fail(DMIP_ERR_UNSUPPORTED, "no compiled log-likelihood kernel (mode " + std::to_string(mode) + ") for width " +
+                                          std::to_string(net->width) + ", layers " + std::to_string(net->n_hidden) +
+                                          ", xdim " + std::to_string(xdim));
+  if (n == 0) return DMIP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  dmip::F32FlowParams p{};
+  p.net[0] = f32_net(net);
+  if (net1) p.net[1] = f32_net(net1);
+  p.n_hidden = net->n_hidden;
+  // y is constant per y index: layer 1 over (x, t) with W1_y y + b1 folded into the bias column (as the samplers)
+  float* l1y = nullptr;
+  const int k1q = (xdim + 2 + 3) / 4;
+  hipError_t e = hipMallocAsync((void**)&l1y, (size_t)n_y * (net->width / 16) * k1q * 64 * sizeof(float), st);
+  if (e != hipSuccess) return fail(DMIP_ERR_ALLOC, std::string("hipMallocAsync: ") + hipGetErrorString(e));
+  dmip::F32L1PrepParams lp{net->w1, net->b1, y_dev, l1y, net->width, net->in_dim, xdim, ydim, k1q};
+  if ((e = dmip::launch_f32_l1_prep(lp, n_y, st)) != hipSuccess) {
+    (void)hipFreeAsync(l1y, st);
+    return hip_fail(e, "f32 layer-1 prep launch");
+  }
+  p.l1y = l1y;
+  p.x = x_dev;
+  p.logp = logp_out_dev;
+  p.latent = latent_out_dev;
+  p.n = n;
+  p.num_steps = num_steps;
+  p.T = (float)sde->T;
+  p.bmin = (float)sde->beta_min;
+  p.bdiff = (float)(sde->beta_max - sde->beta_min);
+  p.h = (float)(sde->T / (double)num_steps);
+  bool ok = false;
+  e = dmip::launch_f32_flow(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  (void)hipFreeAsync(l1y, st);
+  if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled log-likelihood kernel");
+  if (e != hipSuccess) return hip_fail(e, "flow_logp launch");
+  return DMIP_OK;
 }
 
 int dmip_em_sample_stamps(const dmip_mlp* net, const dmip_vpsde* sde, const float* y_dev, int n_y, int ydim,

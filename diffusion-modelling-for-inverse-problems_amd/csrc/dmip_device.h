@@ -110,9 +110,15 @@ struct StepCoef {
   float tau;   // T - t_i, the time the net and coefficients see (sdes.py:78)
   float beta;  // beta(T - t_i)                                    (sdes.py:21-22)
   float g;     // sqrt(beta) (pow 0.5)                             (sdes.py:33-35)
+  // the lambda family of reverse processes (sdes.py:77-87; lmbd = 0 the reverse SDE, 1 the probability-flow ODE):
+  float g_mu;  // fl((1 - 0.5 lmbd) g): the drift's diffusion factor; == g bit for bit at lmbd = 0
+  float g_sig; // fl((1 - lmbd)^0.5 g): the noise term's;             == g bit for bit at lmbd = 0
 };
 
-__device__ __forceinline__ StepCoef step_coef(int i, int S, float T, float bmin, float bdiff) {
+// c_mu = (float)(1 - 0.5 lmbd), c_sig = (float)sqrt(1 - lmbd): the Python scalars as torch rounds them to the
+// tensor's f32 before the multiply (host-computed in double, rounded once)
+__device__ __forceinline__ StepCoef step_coef(int i, int S, float T, float bmin, float bdiff, float c_mu = 1.0f,
+                                              float c_sig = 1.0f) {
   StepCoef c;
   const float ts = __fmul_rn(linspace_at(i, S), T);
   c.tau = __fsub_rn(T, ts);
@@ -120,6 +126,8 @@ __device__ __forceinline__ StepCoef step_coef(int i, int S, float T, float bmin,
   // correctly rounded sqrt: the f64 square root is correctly rounded and rounding it to f32 is
   // innocuous (53 >= 2*24 + 2); hipcc's f32 __fsqrt_rn is not correctly rounded on gfx950
   c.g = (float)__dsqrt_rn((double)c.beta);
+  c.g_mu = __fmul_rn(c_mu, c.g);
+  c.g_sig = __fmul_rn(c_sig, c.g);
   return c;
 }
 
@@ -135,13 +143,13 @@ __device__ __forceinline__ float vp_std(float t, float bmin, float bdiff) {
   return (float)__dsqrt_rn((double)var);  // var ** 0.5, correctly rounded
 }
 
-// x <- fl(x + fl(delta*mu)) + fl(fl(sqrt(delta)*g)*xi),  mu = fl(g*a) - fl(fl(-0.5*beta)*x)
-// (models/diffusion.py:40-42 with sdes.py:77-79,86-87 at lambda = 0).
+// x <- fl(x + fl(delta*mu)) + fl(fl(sqrt(delta)*g_sig)*xi),  mu = fl(g_mu*a) - fl(fl(-0.5*beta)*x)
+// (models/diffusion.py:40-42 with sdes.py:77-79,86-87: ((1 - 0.5 lmbd) g) a - f and sqrt(delta) ((1 - lmbd)^0.5 g) xi).
 __device__ __forceinline__ float em_update(float x, float a, float xi, const StepCoef& c,
                                            float delta, float sqrt_delta) {
-  const float mu = __fsub_rn(__fmul_rn(c.g, a), __fmul_rn(__fmul_rn(-0.5f, c.beta), x));
+  const float mu = __fsub_rn(__fmul_rn(c.g_mu, a), __fmul_rn(__fmul_rn(-0.5f, c.beta), x));
   const float drift = __fadd_rn(x, __fmul_rn(delta, mu));
-  return __fadd_rn(drift, __fmul_rn(__fmul_rn(sqrt_delta, c.g), xi));
+  return __fadd_rn(drift, __fmul_rn(__fmul_rn(sqrt_delta, c.g_sig), xi));
 }
 
 // Trajectory snapshots: x of a chain after every `every`-th step (0-based step i, i + 1 a multiple

@@ -533,7 +533,7 @@ __global__ void __launch_bounds__(NW * 64, 1) dps_x3_kernel(DpsX3Params p) {
   for (int i = 0; i < S; ++i) {
     const float4 c4 = ((const float4*)p.coef)[2 * i];      // tau, beta, g (dmip_device.h step_coef)
     const float4 c5 = ((const float4*)p.coef)[2 * i + 1];  // mean_weight, var (vp_mean_weight, vp_std^2)
-    const StepCoef cf{c4.x, c4.y, c4.z};
+    const StepCoef cf{c4.x, c4.y, c4.z, c4.z, c4.z};
     const float mw = c5.x, var = c5.y;
     for (int d = 0; d < 3; ++d) oor |= beyond_fp16(x[d]);
 

@@ -56,6 +56,7 @@ struct SamplerParams {
   long long chain_offset;     // global index of chain 0 (keys the RNG)
   int num_steps;
   float T, bmin, bdiff, delta, sqrt_delta, mean, stdv;
+  float c_mu, c_sig;          // (float)(1 - 0.5 lmbd), (float)sqrt(1 - lmbd): step_coef's lambda factors (1, 1: the SDE)
   unsigned long long seed;
   unsigned long long* stamps; // diagnostic build only: [n_wg * NW][3] phase cycle sums, else null
   // hand-over of split tiles between waves (set by launch_sampler): per y and wave of the grid, the
@@ -263,6 +264,7 @@ struct F32SamplerParams {
   long long n_chains, chain_offset;
   int num_steps;
   float T, bmin, bdiff, delta, sqrt_delta, mean, stdv;
+  float c_mu, c_sig;          // step_coef's lambda factors (as SamplerParams)
   unsigned long long seed;
   // balanced schedule (as SamplerParams): hand-over state and flags per y and grid wave, the device
   // status word, the consumer's spin bound and the test hook (bit 0: producers never publish)
@@ -294,6 +296,23 @@ struct F32L1PrepParams {
   float* l1y;       // out: [n_y][width/16][k1q][64]
   int width, in_dim, xdim, ydim, k1q;
 };
+
+// log p(x | y) along the probability-flow ODE (dmip_flow.hip): Heun steps on the forward time grid, the divergence
+// from forward tangents (4 rows x (primal + 3 tangents) per wave pass)
+struct F32FlowParams {
+  F32Net net[2];              // net 0: CDE / likelihood; net 1: the Posterior prior
+  const float* l1y;           // per-y layer-1 images [n_y][W/16][K1Q][64] (y folded in)
+  int n_hidden;
+  const float* x;             // [n_y][n][D]
+  float* logp;                // [n_y][n]
+  float* latent;              // [n_y][n][D] x_S, or null
+  long long n;                // rows per y
+  int num_steps;
+  float T, bmin, bdiff, h;    // h = T / num_steps
+};
+hipError_t launch_f32_flow(const F32FlowParams& p, int mode, int width, int n_hidden, int xdim, int ydim, int n_y,
+                           hipStream_t st, bool* supported);
+bool f32_flow_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 
 hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, int n_hidden, int xdim, int ydim,
                               int n_y, hipStream_t st, bool* supported);
@@ -332,13 +351,14 @@ struct X3SamplerParams {
   long long n_chains, chain_offset;
   int num_steps;
   float T, bmin, bdiff, delta, sqrt_delta, mean, stdv;
+  float c_mu, c_sig;          // step_coef's lambda factors (as SamplerParams)
   unsigned long long seed;
   float* xfer;                // balanced schedule hand-over (as SamplerParams)
   unsigned int* xflag;
   unsigned int* err;
   unsigned int spin_limit;
   int debug_flags;
-  const float* coef;          // x3k: per-step (tau, beta, g, 0) [num_steps][4] of step_coef (its launch fills it)
+  const float* coef;          // x3k: per-step (tau, beta, g_mu, g_sig) [num_steps][4] of step_coef (its launch fills it)
   // the width-64 latency engine (dmip_x3s.h) with bias_y null: layer 1's per-y bias from W1 [W][l1_in], b1 and y_obs
   // [n_y][ydim] in the kernel, as x3_bias_prep_kernel forms it (no prep launch, no allocation)
   const float* l1w;

@@ -495,7 +495,7 @@ em_sampler_kernel(SamplerParams p) {
   for (int i = sg.s0; i < sg.s1; ++i) {
     unsigned long long t0 = 0, t1 = 0, t2 = 0;
     if constexpr (STAMP) t0 = stamp();
-    const StepCoef cf = step_coef(sg.kind == 3 ? 0 : i, S, p.T, p.bmin, p.bdiff);
+    const StepCoef cf = step_coef(sg.kind == 3 ? 0 : i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
     float v[NV];
 #pragma unroll
     for (int k = 0; k < D; ++k) v[k] = x[k];

@@ -666,7 +666,7 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
     SnapCursor snap(p.snap_every, sg.s0);
     for (int i0 = sg.s0; i0 < sg.s1; ++i0) {
       const int i = sg.kind == 3 ? 0 : i0;  // idle steps: a dummy tile at step 0, discarded
-      const StepCoef cf = step_coef(i, S, p.T, p.bmin, p.bdiff);
+      const StepCoef cf = step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
       float v[C::NV];
 #pragma unroll
       for (int k = 0; k < D; ++k) v[k] = x[k];

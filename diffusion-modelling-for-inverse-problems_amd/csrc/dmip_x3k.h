@@ -635,7 +635,9 @@ __global__ void __launch_bounds__(KWaves<NT>::NWV * 64, KWaves<NT>::NWV / 4) x3k
     for (int i0 = sg.s0; i0 < sg.s1; ++i0) {
       const int i = sg.kind == 3 ? 0 : i0;  // idle steps: a dummy job at step 0, discarded
       const float4 c4 = ((const float4*)p.coef)[i];  // step_coef(i, ...) of this launch (x3k_coef_kernel)
-      const StepCoef cf{c4.x, c4.y, c4.z};
+      // the table holds g_mu and g_sig, which is all em_update takes; g itself is not carried, and is NaN so that
+      // any later use of cf.g in this kernel shows at once
+      const StepCoef cf{c4.x, c4.y, __builtin_nanf(""), c4.z, c4.w};
       uint64_t t0 = 0;
       if constexpr (DIAG & 2) t0 = stamp();
 
@@ -789,14 +791,15 @@ __global__ void __launch_bounds__(KWaves<NT>::NWV * 64, KWaves<NT>::NWV / 4) x3k
 
 }  // namespace x3k
 
-// the launch's step coefficients: coef[i] = step_coef(i) (the kernel loads them instead of recomputing a division
-// and an f64 square root at every step; the same device function, so the same bits)
+// the launch's step coefficients: coef[i] = (tau, beta, g_mu, g_sig) of step_coef(i) (the kernel loads them instead of
+// recomputing a division and an f64 square root at every step; the same device function, so the same bits; at
+// lmbd = 0 both diffusion factors are g)
 template <int DUMMY = 0>
-__global__ void x3k_coef_kernel(float4* coef, int S, float T, float bmin, float bdiff) {
+__global__ void x3k_coef_kernel(float4* coef, int S, float T, float bmin, float bdiff, float c_mu, float c_sig) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < S) {
-    const StepCoef c = step_coef(i, S, T, bmin, bdiff);
-    coef[i] = make_float4(c.tau, c.beta, c.g, 0.0f);
+    const StepCoef c = step_coef(i, S, T, bmin, bdiff, c_mu, c_sig);
+    coef[i] = make_float4(c.tau, c.beta, c.g_mu, c.g_sig);
   }
 }
 
@@ -821,7 +824,7 @@ inline hipError_t launch_x3k_sampler_t(const X3SamplerParams& p, int n_y, hipStr
     return e;
   }
   hipLaunchKernelGGL(x3k_coef_kernel<0>, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, coef, S, p.T, p.bmin,
-                     p.bdiff);
+                     p.bdiff, p.c_mu, p.c_sig);
   q.coef = (const float*)coef;
   hipLaunchKernelGGL(kern, dim3((unsigned)g, (unsigned)n_y), dim3(NWV * 64), 0, st, q);
   e = hipGetLastError();

@@ -655,13 +655,13 @@ __global__ void __launch_bounds__(NWV * 64, 1) x3p_sampler_kernel(X3SamplerParam
 #pragma unroll
       for (int k = 0; k < D; ++k) e.aP[t][k] = 0.0f;
     const int i_first = sg.kind == 3 ? 0 : sg.s0;
-    e.cf_prev = step_coef(i_first, S, p.T, p.bmin, p.bdiff);
+    e.cf_prev = step_coef(i_first, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
     e.prologue_a(e.cf_prev.tau);
     e.first = true;
 
     for (int i0 = sg.s0; i0 < sg.s1; ++i0) {
       const int i = sg.kind == 3 ? 0 : i0;  // idle steps: a dummy job at step 0, discarded
-      e.cf_cur = step_coef(i, S, p.T, p.bmin, p.bdiff);
+      e.cf_cur = step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
       e.tau_next = step_coef(sg.kind == 3 ? 0 : (i + 1 < S ? i + 1 : i), S, p.T, p.bmin, p.bdiff).tau;
       size_t nA = 0, nB = 0;
       if constexpr (NOISE) {

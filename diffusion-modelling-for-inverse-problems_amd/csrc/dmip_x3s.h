@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(NWS * 64) x3s_sampler_kernel(X3SamplerParams p
     }
     SnapCursor snap(p.snap_every, 0);
     for (int i = 0; i < S; ++i) {
-      const StepCoef cf = step_coef(i, S, p.T, p.bmin, p.bdiff);
+      const StepCoef cf = step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
       float v[NV];
 #pragma unroll
       for (int k = 0; k < D; ++k) v[k] = x[k];

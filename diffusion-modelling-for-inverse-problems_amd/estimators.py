@@ -7,6 +7,10 @@ reverse-SDE kernel for all num_steps, the chain state never leaving the register
   * PosteriorDiffusionEstimator: dmip_em_sample_posterior (prior + likelihood networks in one kernel);
   * CDiffE (repaired sampler): dmip_em_sample_cdiffe;
   * DPS (BASELINE config 4, prior score net + forward-model guidance): dmip_dps_sample.
+CDE and PosteriorDiffusionEstimator sample the whole lambda family of the reference's PluginReverseSDE
+(sdes.py:77-87) with `lmbd=`: 0 the reverse SDE (the default), 1 the deterministic probability-flow ODE
+(dmip_em_sample_lmbd), and `model.log_prob(x, y)` is the model's own log-density log p(x | y) along that ODE
+(dmip_flow_logp, exact f32).
 Precision (`model.precision`, or `precision=` per call; default from $DMIP_PRECISION, else "fp32x3"):
   "fp32x3" -- the reference's fp32 arithmetic at the fp16 matrix rate: every product as three fp16 MFMAs
              (W_hi h_hi + W_hi h_lo + W_lo h_hi, fp32 accumulation; csrc/dmip_x3.h), tanh by exp2 + rcp.
@@ -65,6 +69,17 @@ def default_precision():
 _MORE_ACCURATE = {"fp16": ("fp32x3", "fp32"), "fp32x3": ("fp32",), "fp32": ()}
 
 
+def _check_lmbd(lmbd, model):
+    """lmbd of sdes.py:77-87 as a float in [0, 1]; CDE and PosteriorDiffusionEstimator only (CDiffE's repaired
+    sampler and DPS's guidance are this project's own semantics: no ODE form of them)."""
+    lmbd = float(lmbd)
+    if not 0.0 <= lmbd <= 1.0:
+        raise ValueError(f"lmbd must be in [0, 1], got {lmbd}")
+    if lmbd != 0.0 and not isinstance(model, (CDE, PosteriorDiffusionEstimator)):
+        raise ValueError(f"{type(model).__name__}: lmbd != 0 is implemented for CDE and PosteriorDiffusionEstimator only")
+    return lmbd
+
+
 def _fused_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,)):
     """The precision a fused kernel runs this shape in: the requested one, else the next more accurate
     one that is compiled (_MORE_ACCURATE); None when none is (per-step loop). `acts`: the networks' activation
@@ -93,23 +108,28 @@ class BaseClassDiffusionModel:
         return self.forward(*args, **kwargs)
 
     # ----------------------------------------------------------------- sampling API
-    def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, precision=None):
+    def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, precision=None, lmbd=0.0):
         """Posterior samples for one observation y (ydim,): np.ndarray (num_samples, xdim) float32
         (models/diffusion.py:27-46). Under torch.distributed with world_size > 1 the chains are
         sharded over the ranks and every rank returns all num_samples (parallel.sample_sharded).
-        `precision` overrides self.precision for this call."""
+        `precision` overrides self.precision for this call; `lmbd` in [0, 1] selects the reverse process of
+        sdes.py:77-87 (0: the reverse SDE, 1: the deterministic probability-flow ODE; CDE and Posterior only)."""
         from . import parallel
+        lmbd = _check_lmbd(lmbd, self)
         # (sample_sharded's launch is guarded: the device status word was read after it, so an asynchronous kernel
         # failure has raised already rather than coming back as silent NaNs)
-        x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std, precision=precision)
+        kw = {"lmbd": lmbd} if lmbd != 0.0 else {}
+        x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std, precision=precision, **kw)
         return x.cpu().numpy()
 
     def sample_trajectory(self, y, num_samples=2000, num_steps=200, snapshot_every=10, mean=0, std=1, seed=None,
-                          chain_offset=0, precision=None, corrector_steps=0, snr=0.16):
+                          chain_offset=0, precision=None, corrector_steps=0, snr=0.16, lmbd=0.0):
         """The fused sampler with trajectory snapshots (dmip_em_sample_snapshots): returns device tensors
         (x (n_y, num_samples, xdim), snaps (num_steps // snapshot_every, n_y, num_samples, xdim)), snaps[k]
         = the chains after step (k + 1) * snapshot_every of the loop of models/diffusion.py:27-46 (the
-        reference returns only the final state). Same chains, RNG and sharding as sample_device."""
+        reference returns only the final state). Same chains, RNG and sharding as sample_device; `lmbd` as
+        forward (dmip_em_sample_lmbd with snapshots)."""
+        lmbd = _check_lmbd(lmbd, self)
         if isinstance(self, PosteriorDiffusionEstimator):
             score = self.sde.a
             nets, mode = [score.prior_net, score.likelihood_net], _lib.DMIP_SAMPLER_POSTERIOR
@@ -132,9 +152,57 @@ class BaseClassDiffusionModel:
         snaps = torch.empty(int(num_steps) // int(snapshot_every), ys.shape[0], int(num_samples), self.xdim,
                             device=dev, dtype=torch.float32)
         seed = _draw_seed() if seed is None else seed
+        if lmbd != 0.0:
+            if not 1 <= int(snapshot_every) <= int(num_steps):
+                raise ValueError("snapshot_every must be in [1, num_steps]")
+            _lib.em_sample_lmbd(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, lmbd,
+                                out, None, snapshot_every, snaps, prec)
+            return out, snaps
         _lib.em_sample_snapshots(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed,
                                  snapshot_every, snaps, out, corrector_steps, snr, prec)
         return out, snaps
+
+    def log_prob(self, x, y, num_steps=200, return_latent=False):
+        """The model's own log-density log p(x | y) by the instantaneous change of variables along the
+        probability-flow ODE (lmbd = 1; Song et al. 2021, section 4.3): num_steps Heun steps from x to the latent
+        x_S ~ N(0, I), the divergence of the score network exact (forward tangents), in exact f32 in one launch
+        (dmip_flow_logp). x (n, xdim) with one y (ydim,) -> a float32 device tensor (n,); x (n_y, n, xdim) with ys
+        (n_y, ydim) -> (n_y, n). return_latent=True: (logp, x_S), x_S shaped as x. CDE and
+        PosteriorDiffusionEstimator; like sampling there is no CPU path, and a shape or activation without a
+        compiled kernel raises ValueError."""
+        if isinstance(self, PosteriorDiffusionEstimator):
+            score = self.sde.a
+            nets, mode = [score.prior_net, score.likelihood_net], _lib.DMIP_SAMPLER_POSTERIOR
+        elif isinstance(self, CDE):
+            nets, mode = [self.sde.a], _lib.DMIP_SAMPLER_CDE
+        else:
+            raise ValueError(f"{type(self).__name__}: log_prob is implemented for CDE and PosteriorDiffusionEstimator "
+                             "only")
+        layers = [list(n.hidden_layers) for n in nets]
+        widths = set(w for hl in layers for w in hl)
+        if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
+                not _lib.flow_logp_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode):
+            raise ValueError(f"log_prob: no compiled log-likelihood kernel for hidden layers {layers}, xdim {self.xdim}")
+        if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
+            raise ValueError("log_prob: the log-likelihood kernel computes the tanh chain only")
+        from . import parallel
+        x = torch.as_tensor(x)
+        single = x.ndim == 2
+        dev = x.device if x.is_cuda else self._exec_device(y)
+        dev, ys, sde, _ = self._prepare(torch.as_tensor(y).to(dev), 0, num_steps, nets)
+        xs = x.to(device=dev, dtype=torch.float32)
+        xs = (xs[None] if single else xs).contiguous()
+        if xs.ndim != 3 or xs.shape[0] != ys.shape[0] or xs.shape[2] != self.xdim:
+            raise ValueError("x must be (n, xdim) for one y (ydim,), or (n_y, n, xdim) for ys (n_y, ydim)")
+        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
+        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        logp = torch.empty(xs.shape[0], xs.shape[1], device=dev, dtype=torch.float32)
+        latent = torch.empty_like(xs) if return_latent else None
+        # guarded: the device status word is read after the launch
+        parallel.guarded(dev, lambda: _lib.flow_logp(mode, net, prior, sde, xs, ys, num_steps, logp, latent))
+        if single:
+            logp, latent = logp[0], (latent[0] if return_latent else None)
+        return (logp, latent) if return_latent else logp
 
     def _exec_device(self, y):
         if isinstance(y, torch.Tensor) and y.is_cuda:
@@ -152,11 +220,12 @@ class BaseClassDiffusionModel:
         return ys.reshape(-1, self.ydim).contiguous()
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None):
+                      noise=None, precision=None, lmbd=0.0):
         """Device-resident samples (n_y, num_samples, xdim) for ys (n_y, ydim) -- no host copy.
         `chain_offset` selects a shard of a larger run; `noise` injects standard normals
         (num_steps + 1, n_y, num_samples, xdim) (slot 0 -> x0) in place of the internal RNG;
-        `precision` ("fp32x3" | "fp32" | "fp16") overrides self.precision."""
+        `precision` ("fp32x3" | "fp32" | "fp16") overrides self.precision; `lmbd` as forward (a chain's x0 and its
+        RNG consumption do not depend on it: at lmbd = 1 the normals are drawn and multiplied by 0)."""
         raise NotImplementedError
 
     def _prepare(self, y, num_samples, num_steps, nets):
@@ -220,7 +289,8 @@ class CDE(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None):
+                      noise=None, precision=None, lmbd=0.0):
+        lmbd = _check_lmbd(lmbd, self)
         net = self.sde.a
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [net])
         handle = net.dmip_handle(dev, self.xdim)
@@ -237,10 +307,14 @@ class CDE(BaseClassDiffusionModel):
             base = self.sde.base_sde
 
             def drift(x, y, tvec):
-                return base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
+                return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
 
             return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
-                                   drift, self.xdim, self.xdim)
+                                   drift, self.xdim, self.xdim, lmbd=lmbd)
+        if lmbd != 0.0:
+            _lib.em_sample_lmbd(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps,
+                                mean, std, seed, lmbd, out, noise, precision=prec)
+            return out
         _lib.em_sample(handle, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, noise, prec)
         return out
 
@@ -280,7 +354,7 @@ def _loop_normals(seed, chain_offset, stream_id, n, d, dev):
 
 
 def _em_device_loop(model, ys, num_samples, num_steps, mean, std, seed, chain_offset, drift, zdim,
-                    keep, y_resample=None):
+                    keep, y_resample=None, lmbd=0.0):
     """Reverse-SDE EM loop on device tensors for shapes without a compiled fused sampler: the
     network evaluations are dmip_mlp_forward launches in the networks' own forward precision
     (nets.MLP.dmip_precision, exact f32 unless set otherwise), the update follows
@@ -308,7 +382,7 @@ def _em_device_loop(model, ys, num_samples, num_steps, mean, std, seed, chain_of
                     eps_y = _loop_normals(seed, off, sid + (1 << 39) + i, num_samples, model.ydim, dev)
                 z_in = x if y_resample is None else y_resample(x, y, tau, eps_y)
                 mu = drift(z_in, y, tvec)
-                sigma = base.g(tvec, z_in)
+                sigma = base.g(tvec, z_in) if lmbd == 0.0 else (1. - lmbd) ** 0.5 * base.g(tvec, z_in)
                 xi = _loop_normals(seed, off, sid + 1 + i, num_samples, z_in.shape[1], dev)
                 z = z_in + delta * mu + delta ** 0.5 * sigma * xi
                 x = z[:, :keep] if keep < z.shape[1] else z
@@ -331,7 +405,7 @@ class CDiffE(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
     def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, corrector_steps=0, snr=0.16,
-                precision=None):
+                precision=None, lmbd=0.0):
         """As BaseClassDiffusionModel.forward; `corrector_steps` > 0 adds Langevin corrector steps
         before every predictor step (predictor-corrector sampling, BASELINE config 3; see
         dmip_em_sample_cdiffe in include/dmip.h for the definition). The step size takes the norms at
@@ -339,12 +413,14 @@ class CDiffE(BaseClassDiffusionModel):
         (that one measures |s| on the batch; for a trained score with |s| != sqrt(d)/std the same value
         gives a different step)."""
         from . import parallel
+        _check_lmbd(lmbd, self)  # (raises for lmbd != 0: the repaired CDiffE sampler has no ODE form)
         x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std,
                                     corrector_steps=corrector_steps, snr=snr, precision=precision)
         return x.cpu().numpy()  # (the guarded launch read the device status word)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, corrector_steps=0, snr=0.16, precision=None):
+                      noise=None, corrector_steps=0, snr=0.16, precision=None, lmbd=0.0):
+        _check_lmbd(lmbd, self)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         net = self.sde.a
@@ -408,7 +484,8 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         self.loss_fn = PosteriorLoss
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None):
+                      noise=None, precision=None, lmbd=0.0):
+        lmbd = _check_lmbd(lmbd, self)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         score = self.sde.a
@@ -420,6 +497,10 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         if (prior.width, prior.n_hidden) == (lik.width, lik.n_hidden):
             prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width,
                                     lik.n_hidden, self.xdim, self.ydim, [prior.act, lik.act])
+        if prec is not None and lmbd != 0.0:
+            _lib.em_sample_lmbd(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset, num_steps,
+                                mean, std, seed, lmbd, out, precision=prec)
+            return out
         if prec is not None:
             _lib.em_sample_posterior(prior, lik, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed,
                                      out, prec)
@@ -427,10 +508,10 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         base = self.sde.base_sde
 
         def drift(x, y, tvec):
-            return base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
+            return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
 
         return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
-                               drift, self.xdim, self.xdim)
+                               drift, self.xdim, self.xdim, lmbd=lmbd)
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         """models/diffusion.py:204-229. On a HIP device with PosteriorLoss on the scatterometry surrogate,
@@ -504,11 +585,12 @@ class DPS(BaseClassDiffusionModel):
         return m
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, noise=None,
-                      precision=None):
+                      precision=None, lmbd=0.0):
         """dmip_dps_sample_ex at `precision` (default self.precision): "fp32x3" (the reference's fp32 accuracy at
         the fp16 matrix rate, dmip_dps_x3.hip; also what "fp16" runs: there is no 16-bit DPS) or "fp32" (exact f32,
         forward tangents). At the default precision a chain outside fp16's range resamples in exact f32
         (parallel.sample_checked)."""
+        _check_lmbd(lmbd, self)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         from .problems import surrogate_handle

@@ -169,6 +169,30 @@ int dmip_em_sample_snapshots(int mode, const dmip_mlp* net, const dmip_mlp* prio
                              int num_steps, float mean, float stdv, uint64_t seed, int precision, int corrector_steps,
                              float snr, int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream);
 
+/* The lambda family of reverse processes (sdes.py:77-87): drift ((1 - 0.5 lmbd) g) a - f and diffusion
+ * (1 - lmbd)^0.5 g; lmbd = 0 is the reverse SDE of the entry points above (which call the same code with lmbd = 0,
+ * bit for bit), lmbd = 1 the deterministic probability-flow ODE. mode: DMIP_SAMPLER_CDE (net; prior ignored; noise_dev
+ * as dmip_em_sample) or DMIP_SAMPLER_POSTERIOR (net = the likelihood, prior = the prior; noise_dev null). The RNG
+ * consumption per chain does not depend on lmbd (at lmbd = 1 the normals are drawn and multiplied by 0), so a chain's
+ * x0 is the same for every lmbd. snapshot_every = 0: no snapshots (snap_out_dev ignored); else as
+ * dmip_em_sample_snapshots. lmbd outside [0, 1]: DMIP_ERR_INVALID. */
+int dmip_em_sample_lmbd(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                        int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                        float stdv, uint64_t seed, int precision, double lmbd, const float* noise_dev,
+                        int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream);
+
+/* The model's log-density log p(x | y) by the instantaneous change of variables along the probability-flow ODE
+ * (Song et al. 2021, section 4.3), exact f32, one launch: Heun steps on the forward grid tau_k = linspace(0, 1)[k] T,
+ * h = T / num_steps, v = -1/2 beta x - 1/2 g a, the divergence of a from forward tangents through the network,
+ *   log p = -(d/2) log 2 pi - 1/2 |x_S|^2 + (h/2) sum_k (div v(x_k, tau_k) + div v(x~_k, tau_{k+1}))   (f64 sum).
+ *   x_dev [n_y][n][xdim], y_dev [n_y][ydim]; logp_out_dev [n_y][n]; latent_out_dev [n_y][n][xdim] = x_S, or null.
+ * mode / net / prior as dmip_em_sample_lmbd. Shapes: dmip_flow_logp_supported (what the exact-f32 CDE and Posterior
+ * samplers support; tanh chain only -- a SiLU network is DMIP_ERR_UNSUPPORTED). */
+int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
+                   const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
+                   float* latent_out_dev, void* stream);
+int dmip_flow_logp_supported(int mode, int width, int n_hidden, int xdim, int ydim);
+
 /* ---- training: fused loss value + parameter gradients ----------------------------------------- */
 typedef enum { DMIP_LOSS_DSM = 0, DMIP_LOSS_DSM_PDE = 1, DMIP_LOSS_PINN = 2, DMIP_LOSS_PINN2 = 3 } dmip_loss_kind;
 typedef enum { DMIP_PDE_NONE = 0, DMIP_PDE_FPE = 1, DMIP_PDE_CFPE = 2 } dmip_pde_kind;
