@@ -40,7 +40,10 @@ EXPORTED = (
     "dmip_adam_step", "dmip_em_sample_snapshots", "dmip_train_plan_create", "dmip_train_plan_step",
     "dmip_train_plan_set_counters", "dmip_train_plan_destroy", "dmip_sampler_supported_precision",
     "dmip_dps_sample_ex", "dmip_mh_sample_ex", "dmip_em_sample_lmbd", "dmip_flow_logp", "dmip_flow_logp_supported",
+    "dmip_ode_sample", "dmip_ode_sample_supported",
 )
+DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
+SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
 DMIP_DPS_NLL, DMIP_DPS_NORM = 0, 1
 
 
@@ -132,6 +135,13 @@ def _declare(lib):
         lib.dmip_flow_logp.restype = _i32
         lib.dmip_flow_logp_supported.argtypes = [_i32, _i32, _i32, _i32, _i32]
         lib.dmip_flow_logp_supported.restype = _i32
+    if hasattr(lib, "dmip_ode_sample"):  # (absent from older builds loaded by A/B timing scripts)
+        lib.dmip_ode_sample.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32,
+                                        _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _i32, _c_void_p, _i32,
+                                        _c_void_p, _c_void_p, _c_void_p]
+        lib.dmip_ode_sample.restype = _i32
+        lib.dmip_ode_sample_supported.argtypes = [_i32] * 7
+        lib.dmip_ode_sample_supported.restype = _i32
     if hasattr(lib, "dmip_train_plan_create"):
         lib.dmip_train_plan_create.argtypes = [ctypes.POINTER(DmipTrainPlanDesc), ctypes.POINTER(_c_void_p)]
         lib.dmip_train_plan_step.argtypes = [_c_void_p, _c_void_p, _c_void_p, _c_void_p]
@@ -359,6 +369,31 @@ def em_sample_lmbd(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, 
                                     float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
                                     precision_code(precision), float(lmbd), ptr(noise), int(snapshot_every), ptr(snaps),
                                     ptr(out), stream_of(y.device)))
+
+
+def solver_code(solver):
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {sorted(SOLVERS)}, got {solver!r}")
+    return SOLVERS[solver]
+
+
+def ode_sample_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32x3", solver="heun"):
+    return bool(lib().dmip_ode_sample_supported(mode, width, n_hidden, xdim, ydim, precision_code(precision),
+                                                solver_code(solver)))
+
+
+def ode_sample(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, out, solver="heun",
+               x0=None, snapshot_every=0, snaps=None, precision="fp32x3"):
+    """dmip_ode_sample: the fused CDE / Posterior sampler of the probability-flow ODE; "heun" is the second-order
+    solver (x0 (n_y, n_chains, xdim) replaces the chain's own start state), "euler" dmip_em_sample_lmbd at lmbd = 1."""
+    calls["ode_sample"] = calls.get("ode_sample", 0) + 1
+    _status_pending.add(_dev_index(y.device))
+    n_y, ydim = y.shape
+    check(lib().dmip_ode_sample(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde), ptr(y),
+                                n_y, ydim, net.xdim, int(n_chains), int(chain_offset), int(num_steps), float(mean),
+                                float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), precision_code(precision),
+                                solver_code(solver), ptr(x0), int(snapshot_every), ptr(snaps), ptr(out),
+                                stream_of(y.device)))
 
 
 def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE):

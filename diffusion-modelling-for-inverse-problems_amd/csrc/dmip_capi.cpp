@@ -945,6 +945,8 @@ struct SampleArgs {
   int snap_every = 0;
   float* snap_out_dev = nullptr;
   double lmbd = 0.0;  // sdes.py:77-87: 0 the reverse SDE, 1 the probability-flow ODE (CDE and Posterior)
+  int solver = DMIP_SOLVER_EULER;   // DMIP_SOLVER_HEUN: dmip_ode_sample's second-order ODE steps (lmbd = 1)
+  const float* x0_dev = nullptr;    // Heun: start states [n_y][n_chains][xdim] in place of randn stdv + mean
 };
 
 // step_coef's lambda factors: the Python scalars (1 - 0.5 lmbd) and (1 - lmbd) ** 0.5, evaluated in double and rounded
@@ -1011,6 +1013,8 @@ static int em_sample_f32(int mode, const dmip_mlp* net0, const dmip_mlp* net1, c
   p.debug_flags = debug_no_handover();
   p.spin_limit = p.debug_flags ? (1u << 10) : (1u << 22);
   p.act = f32_act(net0);
+  p.solver = a.solver;
+  p.x0 = a.x0_dev;
   bool ok = false;
   hipError_t e = dmip::launch_f32_sampler(p, mode, net0->width, net0->n_hidden, xdim, ydim, a.n_y, st, &ok);
   if (l1y) (void)hipFreeAsync(l1y, st);
@@ -1055,7 +1059,8 @@ static int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, co
   if (net1) p.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
   p.n_hidden = net0->n_hidden;
   float* bias_y = nullptr;
-  if (dmip::x3s_sampler_eligible(mode, net0->width, net0->n_hidden, xdim, a.n_chains, a.n_y)) {
+  const bool heun = a.solver == DMIP_SOLVER_HEUN;  // the one-tile engine only (dmip_x3.h): x3s / x3k keep Euler
+  if (!heun && dmip::x3s_sampler_eligible(mode, net0->width, net0->n_hidden, xdim, a.n_chains, a.n_y)) {
     // the width-64 latency engine forms the per-y bias itself (round 6: one launch and one allocation fewer)
     p.l1w = net0->w1;
     p.l1b = net0->b1;
@@ -1094,10 +1099,12 @@ static int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, co
   }
   p.debug_flags = debug_no_handover();
   p.spin_limit = p.debug_flags ? (1u << 10) : (1u << 22);
+  p.solver = a.solver;
+  p.x0 = a.x0_dev;
   bool ok = false;
   hipError_t e;
 #ifdef DMIP_WITH_X3P
-  if (mode == DMIP_SAMPLER_CDE && net0->x3p_stream && dmip::x3p_sampler_supported(mode, net0->width, net0->n_hidden, xdim) &&
+  if (!heun && mode == DMIP_SAMPLER_CDE && net0->x3p_stream && dmip::x3p_sampler_supported(mode, net0->width, net0->n_hidden, xdim) &&
       x3k_enabled() && x3p_enabled()) {
     // the paired-tile 32x32 engine at its shape (dmip_x3p.h; A/B library only)
     p.net[0].pstream = net0->x3p_stream;
@@ -1106,7 +1113,7 @@ static int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, co
     e = dmip::launch_x3p_sampler(p, xdim, a.n_y, st, &ok);
   } else
 #endif
-  if (mode == DMIP_SAMPLER_CDE && net0->x3k_stream &&
+  if (!heun && mode == DMIP_SAMPLER_CDE && net0->x3k_stream &&
              dmip::x3k_sampler_supported(mode, net0->width, net0->n_hidden, xdim) && x3k_enabled()) {
     // the k-major multi-tile engine at its shape (dmip_x3k.h)
     p.net[0].kstream = net0->x3k_stream;
@@ -1150,6 +1157,14 @@ static int em_sample_impl(int mode, const dmip_mlp* net0, const dmip_mlp* net1, 
   if (f32_act(net0) || (net1 && f32_act(net1))) {
     if (a.precision != DMIP_PREC_F32 || mode != DMIP_SAMPLER_CDE) return act_refused("em_sample");
   }
+  if (a.solver == DMIP_SOLVER_HEUN &&
+      !(a.precision == DMIP_PREC_F32
+            ? dmip::f32_heun_supported(mode, net0->width, net0->n_hidden, xdim, f32_act(net0))
+            : dmip_ode_sample_supported(mode, net0->width, net0->n_hidden, xdim, ydim, a.precision, a.solver)))
+    return fail(DMIP_ERR_UNSUPPORTED, "no compiled Heun sampler (mode " + std::to_string(mode) + ", precision " +
+                                          std::to_string(a.precision) + ") for width " + std::to_string(net0->width) +
+                                          ", layers " + std::to_string(net0->n_hidden) + ", xdim " +
+                                          std::to_string(xdim));
   if (a.n_chains == 0) return DMIP_OK;
   if (a.precision == DMIP_PREC_F32) return em_sample_f32(mode, net0, net1, a);
   if (a.precision == DMIP_PREC_F32X3) return em_sample_x3(mode, net0, net1, a);
@@ -1311,6 +1326,48 @@ int dmip_em_sample_lmbd(int mode, const dmip_mlp* net, const dmip_mlp* prior, co
   a.snap_every = snapshot_every;
   a.snap_out_dev = snapshot_every > 0 ? snap_out_dev : nullptr;
   a.lmbd = lmbd;
+  return em_sample_impl(mode, net, mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr, a);
+}
+
+// Euler: what dmip_em_sample_lmbd runs (any precision); Heun: the exact-f32 and the one-tile fp32x3 engines (there is
+// no 16-bit Heun kernel). The answer is for the tanh chain, as dmip_sampler_supported_precision's: a SiLU CDE network
+// has its exact-f32 Heun kernel at every shape of the exact-f32 CDE sampler
+int dmip_ode_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision, int solver) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR) return 0;
+  if (solver == DMIP_SOLVER_EULER)
+    return dmip_sampler_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
+  if (solver != DMIP_SOLVER_HEUN) return 0;
+  if (precision == DMIP_PREC_F32) return dmip::f32_heun_supported(mode, width, n_hidden, xdim, 0) ? 1 : 0;
+  if (precision == DMIP_PREC_F32X3) return dmip::x3_heun_supported(mode, width, n_hidden, xdim) ? 1 : 0;
+  return 0;
+}
+
+// the probability-flow ODE sampler (lmbd = 1) by solver; every argument is validated before any device work
+int dmip_ode_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                    int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                    float stdv, uint64_t seed, int precision, int solver, const float* x0_dev, int snapshot_every,
+                    float* snap_out_dev, float* x_out_dev, void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "ode_sample: CDE and Posterior samplers only");
+  if (solver != DMIP_SOLVER_EULER && solver != DMIP_SOLVER_HEUN) return fail(DMIP_ERR_INVALID, "unknown solver");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (snapshot_every < 0 || (snapshot_every > 0 && (snapshot_every > num_steps || !snap_out_dev)))
+    return fail(DMIP_ERR_INVALID, "snapshot_every must be 0 or in [1, num_steps] with a snapshot buffer");
+  if (solver == DMIP_SOLVER_EULER && x0_dev)
+    return fail(DMIP_ERR_UNSUPPORTED, "ode_sample: x0_dev needs DMIP_SOLVER_HEUN (the Euler samplers start from "
+                                      "injected noise: dmip_em_sample_lmbd's noise_dev)");
+  if (!net || !sde || !y_dev || !x_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
+    return fail(DMIP_ERR_INVALID, "null argument");
+  if (solver == DMIP_SOLVER_EULER)
+    return dmip_em_sample_lmbd(mode, net, prior, sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean,
+                               stdv, seed, precision, 1.0, nullptr, snapshot_every, snap_out_dev, x_out_dev, stream);
+  SampleArgs a{sde,  y_dev, n_y,       ydim,      xdim,    n_chains, chain_offset, num_steps,
+               mean, stdv,  seed,      precision, nullptr, x_out_dev, stream,      nullptr};
+  a.snap_every = snapshot_every;
+  a.snap_out_dev = snapshot_every > 0 ? snap_out_dev : nullptr;
+  a.lmbd = 1.0;
+  a.solver = DMIP_SOLVER_HEUN;
+  a.x0_dev = x0_dev;
   return em_sample_impl(mode, net, mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr, a);
 }
 

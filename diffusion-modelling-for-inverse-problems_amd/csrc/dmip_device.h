@@ -152,6 +152,33 @@ __device__ __forceinline__ float em_update(float x, float a, float xi, const Ste
   return __fadd_rn(drift, __fmul_rn(__fmul_rn(sqrt_delta, c.g_sig), xi));
 }
 
+// The second-order sampler of the probability-flow ODE (lmbd = 1: g_mu = fl(0.5 g), no noise term): Heun's
+// explicit trapezoid on the reverse grid of the Euler sampler, tau_i, beta_i, g_i = step_coef(i, S, ...) for
+// i = 0..S (step_coef(S) has tau = 0: linspace_at(S, S) = 1), delta = T / S:
+//     m(x, i) = fl(fl(g_mu_i a(x, y, tau_i)) - fl(fl(-0.5 beta_i) x))        the mu of em_update, unchanged
+//     k1 = m(x_i, i)
+//     x~ = fl(x_i + fl(delta k1))                                            the Euler ODE step
+//     k2 = m(x~, i + 1)
+//     x_{i+1} = fl(x_i + fl(fl(0.5 delta) fl(k1 + k2)))
+// Two network evaluations per step and no draw per step: a chain's x0 is the first draw of its stream (or comes
+// from a buffer), so one seed starts the Euler and the Heun chains from the same x0. For the Posterior estimator
+// a = fl(g_i (lik + prior)) at each stage's own g, as the Euler loop forms it. Both engines (dmip_x3.h,
+// dmip_f32.h) take their arithmetic from here.
+enum { SOLVER_EULER = 0, SOLVER_HEUN = 1 };
+
+struct HeunStep {
+  // m(x, i): the drift of em_update at the coefficients c
+  static __device__ __forceinline__ float slope(float x, float a, const StepCoef& c) {
+    return __fsub_rn(__fmul_rn(c.g_mu, a), __fmul_rn(__fmul_rn(-0.5f, c.beta), x));
+  }
+  static __device__ __forceinline__ float predict(float x, float k1, float delta) {
+    return __fadd_rn(x, __fmul_rn(delta, k1));
+  }
+  static __device__ __forceinline__ float correct(float x, float k1, float k2, float delta) {
+    return __fadd_rn(x, __fmul_rn(__fmul_rn(0.5f, delta), __fadd_rn(k1, k2)));
+  }
+};
+
 // Trajectory snapshots: x of a chain after every `every`-th step (0-based step i, i + 1 a multiple
 // of every) into snap [S / every][n_y][n_chains][D] -- the only HBM writes of a chain before its final
 // state. The cursor holds the next snapshot step of the segment [s0, s1), so a step pays one scalar

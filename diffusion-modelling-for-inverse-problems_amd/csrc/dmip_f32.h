@@ -262,6 +262,8 @@ constexpr int kMaxHidden = 3;  // hidden layers compiled: 1..3 (bias staging bou
 // the balanced WaveSchedule of dmip_device.h (equal segments of C wave-steps, split tiles handed over
 // through global memory), so 100k chains cost 3.05 rounds of the GPU's capacity, not 4. Every lane
 // group of a chain holds the same state, so the hand-over stores all 64 lanes like the 16-bit kernel.
+// SOLVER_HEUN (CDE and Posterior; dmip_f32_{cde,post}_heun.hip): a step is Heun's trapezoid on the probability-flow
+// ODE instead (dmip_device.h HeunStep) -- the network twice, no draw, x0 from p.x0 when given; the rest is unchanged.
 template <int MODE, int W, int D, int M, int ACT = 0>
 struct SamplerCfg {
   static constexpr int NNET = MODE == SAMPLER_POSTERIOR ? 2 : 1;
@@ -273,7 +275,7 @@ struct SamplerCfg {
   using E = FEngine<W, NNET, 1, L::R, L::RING, ACT>;
 };
 
-template <int MODE, int W, int D, int M, bool NOISE, int ACT = 0>
+template <int MODE, int W, int D, int M, bool NOISE, int ACT = 0, int SOLVER = SOLVER_EULER>
 __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32SamplerParams p) {
   using C = SamplerCfg<MODE, W, D, M, ACT>;
   using L = typename C::L;
@@ -336,15 +338,28 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
     } else {
       rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
       float n0[D];
-      if constexpr (NOISE) {
-        const float* src = p.noise + ((size_t)yi * p.n_chains + c_rd) * D;
+      if constexpr (SOLVER == SOLVER_HEUN) {
+        // x0 from the caller's buffer [n_y][n_chains][D], else the first draw of the chain's stream (as Euler's)
+        if (p.x0) {
+          const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
 #pragma unroll
-        for (int k = 0; k < D; ++k) n0[k] = src[k];
+          for (int k = 0; k < D; ++k) x[k] = src[k];
+        } else {
+          rng_normals<D>(rng, n0);
+#pragma unroll
+          for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+        }
       } else {
-        rng_normals<D>(rng, n0);
-      }
+        if constexpr (NOISE) {
+          const float* src = p.noise + ((size_t)yi * p.n_chains + c_rd) * D;
 #pragma unroll
-      for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+          for (int k = 0; k < D; ++k) n0[k] = src[k];
+        } else {
+          rng_normals<D>(rng, n0);
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+      }
     }
 
     SnapCursor snap(p.snap_every, sg.s0);
@@ -376,7 +391,8 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
           float vp[D + 1];
 #pragma unroll
           for (int k = 0; k < D; ++k) vp[k] = vin[k];
-          vp[D] = cf.tau;
+          if constexpr (SOLVER == SOLVER_HEUN) vp[D] = vin[C::NV0 - 1];  // the stage's own time
+          else vp[D] = cf.tau;
           float b1[C::K1Q1];
           l1_operand<D + 1, C::K1Q1>(vp, g, b1);
           f32x4 out1[1];
@@ -411,19 +427,45 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
       }
 
       float a[D];
-      score(v, a);
-      float xi[D];
-      if constexpr (NOISE) {
-        const float* src = p.noise + noise_step * (i + 1) + ((size_t)yi * p.n_chains + c_rd) * D;
+      if constexpr (SOLVER == SOLVER_HEUN) {
+        // Heun's trapezoid on the probability-flow ODE (dmip_device.h HeunStep): the Euler stage, then the same
+        // network evaluation at x~ and step i + 1's coefficients; no draw. The two stages are one loop body: one
+        // inlined copy of the networks, at the register budget of the Euler step (this engine is register-bound
+        // from W = 256 on)
+        static_assert(MODE != SAMPLER_CDIFFE && !NOISE, "Heun: CDE and Posterior, x0 from p.x0 or the RNG");
+        float k1[D];
+#pragma unroll 1
+        for (int stage = 0; stage < 2; ++stage) {
+          const StepCoef c = step_coef(i + stage, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
+          v[C::NV0 - 1] = c.tau;
+          score(v, a);
 #pragma unroll
-        for (int k = 0; k < D; ++k) xi[k] = src[k];
+          for (int k = 0; k < D; ++k) {
+            const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(c.g, a[k]) : a[k];
+            const float m = HeunStep::slope(v[k], ak, c);  // (stage 0: v = x)
+            if (stage == 0) {
+              k1[k] = m;
+              v[k] = HeunStep::predict(x[k], m, p.delta);
+            } else {
+              x[k] = HeunStep::correct(x[k], k1[k], m, p.delta);
+            }
+          }
+        }
       } else {
-        rng_normals<D>(rng, xi);
-      }
+        score(v, a);
+        float xi[D];
+        if constexpr (NOISE) {
+          const float* src = p.noise + noise_step * (i + 1) + ((size_t)yi * p.n_chains + c_rd) * D;
 #pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
-        x[k] = em_update(x[k], ak, xi[k], cf, p.delta, p.sqrt_delta);
+          for (int k = 0; k < D; ++k) xi[k] = src[k];
+        } else {
+          rng_normals<D>(rng, xi);
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
+          x[k] = em_update(x[k], ak, xi[k], cf, p.delta, p.sqrt_delta);
+        }
       }
       snap.at_step<D>(i0, p.snap_every, p.snap_out, gridDim.y, yi, p.n_chains, c_local, sg.kind != 3 && valid && g == 0, x);
     }
@@ -516,10 +558,10 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_forward_kernel(F32Fo
 }  // namespace f32
 
 // ----------------------------------------------------------------- launch helpers (per TU)
-template <int MODE, int W, int D, int M, bool NOISE, int ACT = 0>
+template <int MODE, int W, int D, int M, bool NOISE, int ACT = 0, int SOLVER = SOLVER_EULER>
 inline hipError_t launch_f32_sampler_t(const F32SamplerParams& p, int n_y, hipStream_t st) {
   constexpr int NW = f32::Shape<W>::NW;
-  auto kern = f32::f32_sampler_kernel<MODE, W, D, M, NOISE, ACT>;
+  auto kern = f32::f32_sampler_kernel<MODE, W, D, M, NOISE, ACT, SOLVER>;
   const long long tiles = (p.n_chains + 15) / 16;
   long long g = resident_slots(kern, NW * 64, st) / (n_y > 0 ? n_y : 1);
   const long long cap = (tiles + NW - 1) / NW;
@@ -569,5 +611,9 @@ hipError_t launch_f32_sampler_cde(const F32SamplerParams& p, int width, int xdim
 hipError_t launch_f32_sampler_post(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_f32_sampler_cdiffe(const F32SamplerParams& p, int width, int xdim, int ydim, int n_y, hipStream_t st,
                                      bool* ok);
+// the Heun (probability-flow ODE) instantiations (dmip_f32_{cde,post}_heun.hip; CDE: tanh and SiLU chains by p.act)
+hipError_t launch_f32_sampler_cde_heun(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+hipError_t launch_f32_sampler_post_heun(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st,
+                                        bool* ok);
 
 }  // namespace dmip

@@ -36,6 +36,11 @@ hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, in
   *supported = false;
   if (n_hidden < 1 || n_hidden > f32::kMaxHidden || !f32_sampler_supported(mode, width, n_hidden, xdim, ydim))
     return hipSuccess;
+  if (p.solver == SOLVER_HEUN) {
+    if (!f32_heun_supported(mode, width, n_hidden, xdim, p.act)) return hipSuccess;
+    if (mode == SAMPLER_CDE) return launch_f32_sampler_cde_heun(p, width, xdim, n_y, st, supported);
+    return launch_f32_sampler_post_heun(p, width, xdim, n_y, st, supported);
+  }
   if (mode == SAMPLER_CDE) return launch_f32_sampler_cde(p, width, xdim, n_y, st, supported);
   if (mode == SAMPLER_POSTERIOR) return launch_f32_sampler_post(p, width, xdim, n_y, st, supported);
   return launch_f32_sampler_cdiffe(p, width, xdim, ydim, n_y, st, supported);
@@ -50,6 +55,15 @@ bool f32_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim
   if (mode == SAMPLER_CDE || mode == SAMPLER_POSTERIOR) return xdim == 2 || xdim == 3;
   if (mode == SAMPLER_CDIFFE) return (xdim == 2 && ydim == 2) || (xdim == 3 && ydim == 23);
   return false;
+}
+
+// Heun (dmip_device.h HeunStep): CDE (tanh and SiLU chains, act = F32SamplerParams::act) and Posterior at the shapes of
+// their Euler kernels, less width 512 with the tanh chain: those kernels need scratch (44-176 B per lane; their Euler
+// kernels spill too), and a Heun instantiation that spills is not compiled. The SiLU CDE kernel at 512 is free of it.
+bool f32_heun_supported(int mode, int width, int n_hidden, int xdim, int act) {
+  if (mode != SAMPLER_CDE && mode != SAMPLER_POSTERIOR) return false;
+  if (width == 512 && !(mode == SAMPLER_CDE && act != 0)) return false;
+  return f32_sampler_supported(mode, width, n_hidden, xdim, 0);
 }
 
 // layer-1 k-steps: 2 (in_dim <= 7: every x,t and the linear problem's x,y,t network) or 8 (in_dim

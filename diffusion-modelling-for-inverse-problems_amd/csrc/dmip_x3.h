@@ -562,6 +562,9 @@ __device__ __forceinline__ void report_range(bool oor, unsigned* err, int lane) 
 //                   corrector steps before each predictor step)
 // then mu = g a + 0.5 beta x, x <- x + delta mu + sqrt(delta) g xi (dmip_device.h em_update). Work
 // distribution: the balanced WaveSchedule over 16-chain tiles (as dmip_f32.h).
+// SOLVER_HEUN (CDE and Posterior; dmip_x3_{cde,post}_heun.hip): a step is Heun's trapezoid on the probability-flow
+// ODE instead (dmip_device.h HeunStep) -- the network twice, no draw, x0 from p.x0 when given. Schedule, hand-over,
+// ring and snapshots are the Euler kernel's; every Euler instantiation compiles to what it was without the parameter.
 template <int MODE, int W, int D, int M, int DIAG = 0>
 struct SamplerCfg {
   static constexpr int NNET = MODE == SAMPLER_POSTERIOR ? 2 : 1;
@@ -574,7 +577,7 @@ struct SamplerCfg {
   using E = XEngine<W, NNET, K1Q, L::R, L::RING, DIAG, L1R, L1H>;
 };
 
-template <int MODE, int W, int D, int M, bool NOISE, int DIAG = 0>
+template <int MODE, int W, int D, int M, bool NOISE, int DIAG = 0, int SOLVER = SOLVER_EULER>
 __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sampler_kernel(X3SamplerParams p) {
   using C = SamplerCfg<MODE, W, D, M, DIAG>;
   using L = typename C::L;
@@ -652,15 +655,28 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
     } else {
       rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
       float n0[D];
-      if constexpr (NOISE) {
-        const float* src = p.noise + ((size_t)yi * p.n_chains + c_rd) * D;
+      if constexpr (SOLVER == SOLVER_HEUN) {
+        // x0 from the caller's buffer [n_y][n_chains][D], else the first draw of the chain's stream (as Euler's)
+        if (p.x0) {
+          const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
 #pragma unroll
-        for (int k = 0; k < D; ++k) n0[k] = src[k];
+          for (int k = 0; k < D; ++k) x[k] = src[k];
+        } else {
+          rng_normals<D>(rng, n0);
+#pragma unroll
+          for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+        }
       } else {
-        rng_normals<D>(rng, n0);
-      }
+        if constexpr (NOISE) {
+          const float* src = p.noise + ((size_t)yi * p.n_chains + c_rd) * D;
 #pragma unroll
-      for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+          for (int k = 0; k < D; ++k) n0[k] = src[k];
+        } else {
+          rng_normals<D>(rng, n0);
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+      }
     }
 
     SnapCursor snap(p.snap_every, sg.s0);
@@ -718,18 +734,39 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
 
       float a[D];
       score(v, a);
-      float xi[D];
-      if constexpr (NOISE) {
-        const float* src = p.noise + noise_step * (i + 1) + ((size_t)yi * p.n_chains + c_rd) * D;
+      if constexpr (SOLVER == SOLVER_HEUN) {
+        // Heun's trapezoid on the probability-flow ODE (dmip_device.h HeunStep): the Euler stage, then the same
+        // network evaluation at x~ and step i + 1's coefficients; no draw
+        static_assert(MODE != SAMPLER_CDIFFE && !NOISE, "Heun: CDE and Posterior, x0 from p.x0 or the RNG");
+        float k1[D];
 #pragma unroll
-        for (int k = 0; k < D; ++k) xi[k] = src[k];
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
+          k1[k] = HeunStep::slope(x[k], ak, cf);
+          v[k] = HeunStep::predict(x[k], k1[k], p.delta);
+        }
+        const StepCoef c2 = step_coef(i + 1, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
+        v[C::NV - 1] = c2.tau;
+        score(v, a);
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(c2.g, a[k]) : a[k];
+          x[k] = HeunStep::correct(x[k], k1[k], HeunStep::slope(v[k], ak, c2), p.delta);
+        }
       } else {
-        rng_normals<D>(rng, xi);
-      }
+        float xi[D];
+        if constexpr (NOISE) {
+          const float* src = p.noise + noise_step * (i + 1) + ((size_t)yi * p.n_chains + c_rd) * D;
 #pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
-        x[k] = em_update(x[k], ak, xi[k], cf, p.delta, p.sqrt_delta);
+          for (int k = 0; k < D; ++k) xi[k] = src[k];
+        } else {
+          rng_normals<D>(rng, xi);
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
+          x[k] = em_update(x[k], ak, xi[k], cf, p.delta, p.sqrt_delta);
+        }
       }
       {
         const long long cn = chain_now();
@@ -760,10 +797,10 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
 }  // namespace x3
 
 // ----------------------------------------------------------------- launch helpers (per TU)
-template <int MODE, int W, int D, int M, bool NOISE, int DIAG = 0>
+template <int MODE, int W, int D, int M, bool NOISE, int DIAG = 0, int SOLVER = SOLVER_EULER>
 inline hipError_t launch_x3_sampler_t(const X3SamplerParams& p, int n_y, hipStream_t st) {
   constexpr int NW = x3::Shape<W>::NW;
-  auto kern = x3::x3_sampler_kernel<MODE, W, D, M, NOISE, DIAG>;
+  auto kern = x3::x3_sampler_kernel<MODE, W, D, M, NOISE, DIAG, SOLVER>;
   const long long tiles = (p.n_chains + 15) / 16;
   long long g = resident_slots(kern, NW * 64, st) / (n_y > 0 ? n_y : 1);
   const long long cap = (tiles + NW - 1) / NW;
@@ -794,5 +831,8 @@ hipError_t launch_x3_sampler_cde(const X3SamplerParams& p, int width, int xdim, 
 hipError_t launch_x3_sampler_post(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_x3_sampler_cdiffe(const X3SamplerParams& p, int width, int xdim, int ydim, int n_y, hipStream_t st,
                                     bool* ok);
+// the Heun (probability-flow ODE) instantiations of the one-tile engine (dmip_x3_{cde,post}_heun.hip)
+hipError_t launch_x3_sampler_cde_heun(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+hipError_t launch_x3_sampler_post_heun(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 
 }  // namespace dmip

@@ -50,6 +50,11 @@ hipError_t launch_x3_sampler(const X3SamplerParams& p, int mode, int width, int 
                              hipStream_t st, bool* supported) {
   *supported = false;
   if (!x3_sampler_supported(mode, width, n_hidden, xdim, ydim)) return hipSuccess;
+  if (p.solver == SOLVER_HEUN) {
+    if (!x3_heun_supported(mode, width, n_hidden, xdim)) return hipSuccess;
+    if (mode == SAMPLER_CDE) return launch_x3_sampler_cde_heun(p, width, xdim, n_y, st, supported);
+    return launch_x3_sampler_post_heun(p, width, xdim, n_y, st, supported);
+  }
   if (mode == SAMPLER_CDE) return launch_x3_sampler_cde(p, width, xdim, n_y, st, supported);
   if (mode == SAMPLER_POSTERIOR) return launch_x3_sampler_post(p, width, xdim, n_y, st, supported);
   return launch_x3_sampler_cdiffe(p, width, xdim, ydim, n_y, st, supported);
@@ -64,6 +69,12 @@ bool x3_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim)
   if (mode == SAMPLER_CDE || mode == SAMPLER_POSTERIOR) return xdim == 2 || xdim == 3;
   if (mode == SAMPLER_CDIFFE) return (xdim == 2 && ydim == 2) || (xdim == 3 && ydim == 23);
   return false;
+}
+
+// Heun (dmip_device.h HeunStep): CDE and Posterior at every shape their Euler kernels of this engine have (all of
+// them free of scratch, W = 512 included: DESIGN.md 3e)
+bool x3_heun_supported(int mode, int width, int n_hidden, int xdim) {
+  return (mode == SAMPLER_CDE || mode == SAMPLER_POSTERIOR) && x3_sampler_supported(mode, width, n_hidden, xdim, 0);
 }
 
 }  // namespace dmip

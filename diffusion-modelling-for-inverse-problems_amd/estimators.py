@@ -80,6 +80,53 @@ def _check_lmbd(lmbd, model):
     return lmbd
 
 
+def _check_solver(solver, lmbd, model, x0=None, noise=None):
+    """The effective lmbd of a sampling call. solver="heun" is the second-order sampler of the probability-flow ODE
+    (dmip_ode_sample): lmbd left at its default or given as 1.0, CDE and PosteriorDiffusionEstimator only, no noise
+    to inject. x0= (the chains' start states) needs it."""
+    _lib.solver_code(solver)
+    if solver == "heun":
+        if not isinstance(model, (CDE, PosteriorDiffusionEstimator)):
+            raise ValueError(f"{type(model).__name__}: solver='heun' is implemented for CDE and "
+                             "PosteriorDiffusionEstimator only")
+        if float(lmbd) not in (0.0, 1.0):
+            raise ValueError(f"solver='heun' integrates the probability-flow ODE (lmbd = 1), got lmbd={lmbd}")
+        if noise is not None:
+            raise ValueError("solver='heun' draws no noise per step: pass the start states as x0=")
+        return 1.0
+    if x0 is not None:
+        raise ValueError("x0= needs solver='heun'; the Euler samplers take their start states through the noise= "
+                         "argument (slot 0 of the injected normals)")
+    return _check_lmbd(lmbd, model)
+
+
+def _x0_tensor(x0, ys, num_samples, xdim, dev):
+    """x0 as a contiguous f32 device tensor (n_y, num_samples, xdim); (num_samples, xdim) is accepted for one y."""
+    if x0 is None:
+        return None
+    x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32)
+    if x0.ndim == 2 and ys.shape[0] == 1:
+        x0 = x0[None]
+    if tuple(x0.shape) != (ys.shape[0], int(num_samples), xdim):
+        raise ValueError("x0 must have shape (n_y, num_samples, xdim), or (num_samples, xdim) for one y")
+    return x0.contiguous()
+
+
+def _heun_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,)):
+    """_fused_precision for solver="heun": fp32x3 (the one-tile engine) or fp32; "fp16" runs fp32x3 (there is no
+    16-bit Heun kernel). None: the per-step loop."""
+    _lib.precision_code(precision)
+    precision = canonical_precision(precision)
+    if any(a != _lib.DMIP_ACT_TANH_TWICE_FIRST for a in acts):
+        # (the SiLU chain's Heun kernel: every shape of its exact-f32 CDE sampler)
+        ok = mode == _lib.DMIP_SAMPLER_CDE and _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, "fp32")
+        return "fp32" if ok else None
+    for prec in (precision,) + _MORE_ACCURATE[precision]:
+        if _lib.ode_sample_supported(width, n_hidden, xdim, ydim, mode, prec):
+            return prec
+    return None
+
+
 def _fused_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,)):
     """The precision a fused kernel runs this shape in: the requested one, else the next more accurate
     one that is compiled (_MORE_ACCURATE); None when none is (per-step loop). `acts`: the networks' activation
@@ -108,28 +155,34 @@ class BaseClassDiffusionModel:
         return self.forward(*args, **kwargs)
 
     # ----------------------------------------------------------------- sampling API
-    def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, precision=None, lmbd=0.0):
+    def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, precision=None, lmbd=0.0,
+                solver="euler"):
         """Posterior samples for one observation y (ydim,): np.ndarray (num_samples, xdim) float32
         (models/diffusion.py:27-46). Under torch.distributed with world_size > 1 the chains are
         sharded over the ranks and every rank returns all num_samples (parallel.sample_sharded).
         `precision` overrides self.precision for this call; `lmbd` in [0, 1] selects the reverse process of
-        sdes.py:77-87 (0: the reverse SDE, 1: the deterministic probability-flow ODE; CDE and Posterior only)."""
+        sdes.py:77-87 (0: the reverse SDE, 1: the deterministic probability-flow ODE; CDE and Posterior only).
+        `solver="heun"` samples that ODE with Heun's second-order steps (two network evaluations per step; about
+        an eighth of the Euler steps reach the same accuracy: DESIGN.md 3e), sharded like every other call."""
         from . import parallel
-        lmbd = _check_lmbd(lmbd, self)
+        lmbd = _check_solver(solver, lmbd, self)
         # (sample_sharded's launch is guarded: the device status word was read after it, so an asynchronous kernel
         # failure has raised already rather than coming back as silent NaNs)
         kw = {"lmbd": lmbd} if lmbd != 0.0 else {}
+        if solver != "euler":
+            kw["solver"] = solver
         x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std, precision=precision, **kw)
         return x.cpu().numpy()
 
     def sample_trajectory(self, y, num_samples=2000, num_steps=200, snapshot_every=10, mean=0, std=1, seed=None,
-                          chain_offset=0, precision=None, corrector_steps=0, snr=0.16, lmbd=0.0):
+                          chain_offset=0, precision=None, corrector_steps=0, snr=0.16, lmbd=0.0, solver="euler"):
         """The fused sampler with trajectory snapshots (dmip_em_sample_snapshots): returns device tensors
         (x (n_y, num_samples, xdim), snaps (num_steps // snapshot_every, n_y, num_samples, xdim)), snaps[k]
         = the chains after step (k + 1) * snapshot_every of the loop of models/diffusion.py:27-46 (the
         reference returns only the final state). Same chains, RNG and sharding as sample_device; `lmbd` as
-        forward (dmip_em_sample_lmbd with snapshots)."""
-        lmbd = _check_lmbd(lmbd, self)
+        forward (dmip_em_sample_lmbd with snapshots); `solver="heun"`: the states after each full Heun step
+        (dmip_ode_sample)."""
+        lmbd = _check_solver(solver, lmbd, self)
         if isinstance(self, PosteriorDiffusionEstimator):
             score = self.sde.a
             nets, mode = [score.prior_net, score.likelihood_net], _lib.DMIP_SAMPLER_POSTERIOR
@@ -145,13 +198,19 @@ class BaseClassDiffusionModel:
         net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
         if prior is not None and (prior.width, prior.n_hidden) != (net.width, net.n_hidden):
             raise ValueError("prior and likelihood networks must have the same hidden layers")
-        prec = _fused_precision(precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim,
-                                [h.act for h in handles])
+        prec = (_heun_precision if solver == "heun" else _fused_precision)(
+            precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim, [h.act for h in handles])
         if prec is None:
             raise ValueError("no fused sampler for this network shape / activation")
         snaps = torch.empty(int(num_steps) // int(snapshot_every), ys.shape[0], int(num_samples), self.xdim,
                             device=dev, dtype=torch.float32)
         seed = _draw_seed() if seed is None else seed
+        if solver == "heun":
+            if not 1 <= int(snapshot_every) <= int(num_steps):
+                raise ValueError("snapshot_every must be in [1, num_steps]")
+            _lib.ode_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out,
+                            "heun", None, snapshot_every, snaps, prec)
+            return out, snaps
         if lmbd != 0.0:
             if not 1 <= int(snapshot_every) <= int(num_steps):
                 raise ValueError("snapshot_every must be in [1, num_steps]")
@@ -220,12 +279,17 @@ class BaseClassDiffusionModel:
         return ys.reshape(-1, self.ydim).contiguous()
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0):
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None):
         """Device-resident samples (n_y, num_samples, xdim) for ys (n_y, ydim) -- no host copy.
         `chain_offset` selects a shard of a larger run; `noise` injects standard normals
         (num_steps + 1, n_y, num_samples, xdim) (slot 0 -> x0) in place of the internal RNG;
         `precision` ("fp32x3" | "fp32" | "fp16") overrides self.precision; `lmbd` as forward (a chain's x0 and its
-        RNG consumption do not depend on it: at lmbd = 1 the normals are drawn and multiplied by 0)."""
+        RNG consumption do not depend on it: at lmbd = 1 the normals are drawn and multiplied by 0).
+        `solver="heun"` (CDE and Posterior): Heun's second-order steps along the probability-flow ODE
+        (dmip_ode_sample; fp32x3 on the one-tile engine, or fp32; "fp16" runs fp32x3), from the same x0 as the Euler
+        samplers at the same seed -- or from `x0` (n_y, num_samples, xdim) ((num_samples, xdim) for one y; with
+        chain_offset the rows of this shard), e.g. the latent of log_prob(..., return_latent=True): the two are an
+        encode / decode pair."""
         raise NotImplementedError
 
     def _prepare(self, y, num_samples, num_steps, nets):
@@ -289,14 +353,16 @@ class CDE(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0):
-        lmbd = _check_lmbd(lmbd, self)
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None):
+        lmbd = _check_solver(solver, lmbd, self, x0, noise)
         net = self.sde.a
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [net])
         handle = net.dmip_handle(dev, self.xdim)
         seed = _draw_seed() if seed is None else seed
-        prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_CDE, handle.width, handle.n_hidden,
-                                self.xdim, self.ydim, [handle.act])
+        x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
+        prec = (_heun_precision if solver == "heun" else _fused_precision)(
+            precision or self.precision, _lib.DMIP_SAMPLER_CDE, handle.width, handle.n_hidden, self.xdim, self.ydim,
+            [handle.act])
         if noise is not None:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
             if tuple(noise.shape) != (int(num_steps) + 1, ys.shape[0], int(num_samples), self.xdim):
@@ -310,7 +376,11 @@ class CDE(BaseClassDiffusionModel):
                 return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
 
             return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
-                                   drift, self.xdim, self.xdim, lmbd=lmbd)
+                                   drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
+        if solver == "heun":
+            _lib.ode_sample(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps, mean,
+                            std, seed, out, "heun", x0, precision=prec)
+            return out
         if lmbd != 0.0:
             _lib.em_sample_lmbd(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps,
                                 mean, std, seed, lmbd, out, noise, precision=prec)
@@ -354,13 +424,15 @@ def _loop_normals(seed, chain_offset, stream_id, n, d, dev):
 
 
 def _em_device_loop(model, ys, num_samples, num_steps, mean, std, seed, chain_offset, drift, zdim,
-                    keep, y_resample=None, lmbd=0.0):
+                    keep, y_resample=None, lmbd=0.0, solver="euler", x0=None):
     """Reverse-SDE EM loop on device tensors for shapes without a compiled fused sampler: the
     network evaluations are dmip_mlp_forward launches in the networks' own forward precision
     (nets.MLP.dmip_precision, exact f32 unless set otherwise), the update follows
     models/diffusion.py:40-42 (same rounding order as the fused kernel). Noise comes from the
     kernels' counter-keyed generator, keyed by (seed, global chain index, stream = (y index, step)),
-    so a shard of a run draws exactly the chains of the full run (bit-identical union)."""
+    so a shard of a run draws exactly the chains of the full run (bit-identical union).
+    solver="heun" (lmbd = 1): the two-stage update of csrc/dmip_device.h HeunStep, two network launches per step and
+    no noise; x0 (n_y, num_samples, zdim) replaces the generator's start states."""
     dev = ys.device
     base = model.sde.base_sde
     T = float(model.sde.T)
@@ -373,10 +445,16 @@ def _em_device_loop(model, ys, num_samples, num_steps, mean, std, seed, chain_of
         for k in range(n_y):
             y = ys[k]
             sid = _LOOP_STREAM + (k << 40)
-            x = _loop_normals(seed, off, sid, num_samples, zdim, dev) * std + mean
+            x = x0[k] if x0 is not None else _loop_normals(seed, off, sid, num_samples, zdim, dev) * std + mean
             for i in range(num_steps):
                 tau = (T - ts[i]).item()
                 tvec = torch.full((num_samples, 1), tau, device=dev)
+                if solver == "heun":
+                    k1 = drift(x, y, tvec)
+                    xt = x + delta * k1
+                    k2 = drift(xt, y, torch.full((num_samples, 1), (T - ts[i + 1]).item(), device=dev))
+                    x = x + (0.5 * delta) * (k1 + k2)
+                    continue
                 eps_y = None
                 if y_resample is not None:
                     eps_y = _loop_normals(seed, off, sid + (1 << 39) + i, num_samples, model.ydim, dev)
@@ -405,7 +483,7 @@ class CDiffE(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
     def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, corrector_steps=0, snr=0.16,
-                precision=None, lmbd=0.0):
+                precision=None, lmbd=0.0, solver="euler"):
         """As BaseClassDiffusionModel.forward; `corrector_steps` > 0 adds Langevin corrector steps
         before every predictor step (predictor-corrector sampling, BASELINE config 3; see
         dmip_em_sample_cdiffe in include/dmip.h for the definition). The step size takes the norms at
@@ -413,14 +491,14 @@ class CDiffE(BaseClassDiffusionModel):
         (that one measures |s| on the batch; for a trained score with |s| != sqrt(d)/std the same value
         gives a different step)."""
         from . import parallel
-        _check_lmbd(lmbd, self)  # (raises for lmbd != 0: the repaired CDiffE sampler has no ODE form)
+        _check_solver(solver, lmbd, self)  # (raises for lmbd != 0 or "heun": the repaired sampler has no ODE form)
         x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std,
                                     corrector_steps=corrector_steps, snr=snr, precision=precision)
         return x.cpu().numpy()  # (the guarded launch read the device status word)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, corrector_steps=0, snr=0.16, precision=None, lmbd=0.0):
-        _check_lmbd(lmbd, self)
+                      noise=None, corrector_steps=0, snr=0.16, precision=None, lmbd=0.0, solver="euler", x0=None):
+        _check_solver(solver, lmbd, self, x0)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         net = self.sde.a
@@ -484,8 +562,8 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         self.loss_fn = PosteriorLoss
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0):
-        lmbd = _check_lmbd(lmbd, self)
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None):
+        lmbd = _check_solver(solver, lmbd, self, x0, noise)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         score = self.sde.a
@@ -494,9 +572,15 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         prior = score.prior_net.dmip_handle(dev, self.xdim)
         lik = score.likelihood_net.dmip_handle(dev, self.xdim)
         prec = None
+        x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
         if (prior.width, prior.n_hidden) == (lik.width, lik.n_hidden):
-            prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width,
-                                    lik.n_hidden, self.xdim, self.ydim, [prior.act, lik.act])
+            prec = (_heun_precision if solver == "heun" else _fused_precision)(
+                precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width, lik.n_hidden, self.xdim,
+                self.ydim, [prior.act, lik.act])
+        if prec is not None and solver == "heun":
+            _lib.ode_sample(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset, num_steps,
+                            mean, std, seed, out, "heun", x0, precision=prec)
+            return out
         if prec is not None and lmbd != 0.0:
             _lib.em_sample_lmbd(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset, num_steps,
                                 mean, std, seed, lmbd, out, precision=prec)
@@ -511,7 +595,7 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
             return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
 
         return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
-                               drift, self.xdim, self.xdim, lmbd=lmbd)
+                               drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         """models/diffusion.py:204-229. On a HIP device with PosteriorLoss on the scatterometry surrogate,
@@ -585,12 +669,12 @@ class DPS(BaseClassDiffusionModel):
         return m
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, noise=None,
-                      precision=None, lmbd=0.0):
+                      precision=None, lmbd=0.0, solver="euler", x0=None):
         """dmip_dps_sample_ex at `precision` (default self.precision): "fp32x3" (the reference's fp32 accuracy at
         the fp16 matrix rate, dmip_dps_x3.hip; also what "fp16" runs: there is no 16-bit DPS) or "fp32" (exact f32,
         forward tangents). At the default precision a chain outside fp16's range resamples in exact f32
         (parallel.sample_checked)."""
-        _check_lmbd(lmbd, self)
+        _check_solver(solver, lmbd, self, x0)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         from .problems import surrogate_handle

@@ -193,6 +193,29 @@ int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const d
                    float* latent_out_dev, void* stream);
 int dmip_flow_logp_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 
+/* Sampling along the probability-flow ODE (lmbd = 1) by solver. DMIP_SOLVER_EULER is dmip_em_sample_lmbd at lmbd = 1
+ * (x0_dev null: forwarded, bit for bit; x0_dev given: DMIP_ERR_UNSUPPORTED -- the Euler samplers start from injected
+ * noise, noise_dev). DMIP_SOLVER_HEUN is Heun's explicit trapezoid on the sampler's reverse grid, tau_i, beta_i, g_i
+ * for i = 0..num_steps (tau_S = 0), delta = T / num_steps, g_mu = fl(0.5 g), every operation rounded to f32:
+ *   m(x, i) = g_mu_i a(x, y, tau_i) - (-0.5 beta_i) x
+ *   k1 = m(x_i, i);  x~ = x_i + delta k1;  k2 = m(x~, i + 1);  x_{i+1} = x_i + (0.5 delta) (k1 + k2)
+ * (a = g_i (likelihood + prior) at each stage's own g for DMIP_SAMPLER_POSTERIOR): second order, two network
+ * evaluations per step, no noise drawn per step.
+ *   x0_dev  [n_y][n_chains][xdim] start states (with chain_offset: the rows of this shard), or null: x0 = mean + stdv
+ *           times the first normals of the chain's stream (seed, chain_offset + chain, y index) -- the x0 of every
+ *           other sampler entry point at the same seed, so shards of a run stay bit-identical to the whole run.
+ * snapshot_every / snap_out_dev as dmip_em_sample_lmbd (a snapshot is the state after a full step). precision:
+ * DMIP_PREC_F32 or DMIP_PREC_F32X3 (the one-tile engine; there is no 16-bit Heun kernel: DMIP_PREC_FP16 is
+ * DMIP_ERR_UNSUPPORTED, as is a SiLU network except for the exact-f32 CDE sampler). Modes other than CDE / Posterior,
+ * an unknown solver, null arguments, num_steps < 1 and a bad snapshot_every are DMIP_ERR_INVALID; every argument is
+ * validated before any device work. Shapes: dmip_ode_sample_supported. */
+typedef enum { DMIP_SOLVER_EULER = 0, DMIP_SOLVER_HEUN = 1 } dmip_solver;
+int dmip_ode_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                    int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                    float stdv, uint64_t seed, int precision, int solver, const float* x0_dev, int snapshot_every,
+                    float* snap_out_dev, float* x_out_dev, void* stream);
+int dmip_ode_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision, int solver);
+
 /* ---- training: fused loss value + parameter gradients ----------------------------------------- */
 typedef enum { DMIP_LOSS_DSM = 0, DMIP_LOSS_DSM_PDE = 1, DMIP_LOSS_PINN = 2, DMIP_LOSS_PINN2 = 3 } dmip_loss_kind;
 typedef enum { DMIP_PDE_NONE = 0, DMIP_PDE_FPE = 1, DMIP_PDE_CFPE = 2 } dmip_pde_kind;
