@@ -8,7 +8,10 @@ F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(C
            $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o
-OBJS := $(CSRC)/dmip_kernels.o $(CSRC)/dmip_train.o $(CSRC)/dmip_eval.o $(CSRC)/dmip_surrogate.o $(CSRC)/dmip_gemm.o $(CSRC)/dmip_jets.o $(CSRC)/dmip_step.o $(F32OBJS) $(X3OBJS) $(CSRC)/dmip_capi.o
+# the C-ABI layer by concern: packers and handles, sampling entry points, training entry points
+CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train
+CAPIOBJS := $(patsubst %,$(CSRC)/%.o,$(CAPI))
+OBJS := $(CSRC)/dmip_kernels.o $(CSRC)/dmip_train.o $(CSRC)/dmip_eval.o $(CSRC)/dmip_surrogate.o $(CSRC)/dmip_gemm.o $(CSRC)/dmip_jets.o $(CSRC)/dmip_step.o $(F32OBJS) $(X3OBJS) $(CAPIOBJS)
 HDRS := $(CSRC)/dmip_device.h $(CSRC)/dmip_internal.h include/dmip.h
 
 all: $(PKG)/libdmip.so
@@ -63,7 +66,7 @@ $(CSRC)/dmip_x3k.o: $(CSRC)/dmip_x3k.hip $(CSRC)/dmip_x3k.h $(CSRC)/dmip_x3.h $(
 $(CSRC)/dmip_dps_x3.o: $(CSRC)/dmip_dps_x3.hip $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-$(CSRC)/dmip_capi.o: $(CSRC)/dmip_capi.cpp $(HDRS)
+$(CSRC)/dmip_capi_%.o: $(CSRC)/dmip_capi_%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(PKG)/libdmip.so: $(OBJS)
@@ -76,7 +79,7 @@ $(PKG)/libdmip.so: $(OBJS)
 # per-chunk stamps (scripts/x3p_stamps.py) replace its snapshots, so they need their own build:
 # make diag X3P_DIAG=-DDMIP_X3P_DIAG
 DIAG_DIR := abv/diag
-DIAG_SRCS := dmip_x3_cde dmip_x3k dmip_capi
+DIAG_SRCS := dmip_x3_cde dmip_x3k dmip_capi_pack dmip_capi_sample
 diag: $(DIAG_DIR)/libdmip_diag.so
 $(DIAG_DIR)/%_diag.o: $(CSRC)/%.hip $(CSRC)/dmip_x3k.h $(CSRC)/dmip_x3.h $(CSRC)/dmip_x3s.h $(HDRS)
 	@mkdir -p $(DIAG_DIR)
@@ -85,7 +88,8 @@ X3P_DIAG ?=
 $(DIAG_DIR)/dmip_x3p_diag.o: $(CSRC)/dmip_x3p.hip $(CSRC)/dmip_x3p.h $(CSRC)/dmip_x3.h $(HDRS)
 	@mkdir -p $(DIAG_DIR)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(X3P_DIAG) -c $< -o $@
-$(DIAG_DIR)/dmip_capi_diag.o: $(CSRC)/dmip_capi.cpp $(HDRS)
+# the paired engine's packer (dmip_capi_pack.cpp) and its launch (dmip_capi_sample.cpp)
+$(DIAG_DIR)/dmip_capi_%_diag.o: $(CSRC)/dmip_capi_%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)
 	@mkdir -p $(DIAG_DIR)
 	$(HIPCC) $(HIPFLAGS) -DDMIP_WITH_X3P -c $< -o $@
 $(DIAG_DIR)/libdmip_diag.so: $(filter-out $(patsubst %,$(CSRC)/%.o,$(DIAG_SRCS)),$(OBJS)) $(patsubst %,$(DIAG_DIR)/%_diag.o,$(DIAG_SRCS)) $(DIAG_DIR)/dmip_x3p_diag.o
@@ -98,17 +102,17 @@ scripts/ubench/%: scripts/ubench/%.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 $< -o $@
 
 # Host-only AddressSanitizer build of the C-ABI layer (argument validation, packing, handle
-# management): dmip_capi.cpp instrumented on the host side only (-Xarch_host), linked with the same
-# kernel objects, driven by tests/asan/capi_args.cpp through the calls that need no GPU.
-# dmip_capi.cpp has no device code: it compiles as plain host C++ against the HIP runtime headers.
+# management): every dmip_capi_*.cpp instrumented as host code, linked with the same kernel objects,
+# driven by tests/asan/capi_args.cpp through the calls that need no GPU.
+# The capi sources have no device code: they compile as plain host C++ against the HIP runtime headers.
 ASAN_DIR := build/asan
 HOSTCXX ?= /opt/rocm/lib/llvm/bin/clang++
 ASANFLAGS := -O1 -g -std=c++17 -fPIC -fsanitize=address -fno-omit-frame-pointer
 asan: $(ASAN_DIR)/capi_args
-$(ASAN_DIR)/dmip_capi_asan.o: $(CSRC)/dmip_capi.cpp $(HDRS)
+$(ASAN_DIR)/%_asan.o: $(CSRC)/%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)
 	@mkdir -p $(ASAN_DIR)
 	$(HOSTCXX) -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $(ASANFLAGS) -c $< -o $@
-$(ASAN_DIR)/libdmip_asan.so: $(filter-out $(CSRC)/dmip_capi.o,$(OBJS)) $(ASAN_DIR)/dmip_capi_asan.o
+$(ASAN_DIR)/libdmip_asan.so: $(filter-out $(CAPIOBJS),$(OBJS)) $(patsubst %,$(ASAN_DIR)/%_asan.o,$(CAPI))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -fsanitize=address $^ -o $@
 $(ASAN_DIR)/capi_args: tests/asan/capi_args.cpp $(ASAN_DIR)/libdmip_asan.so include/dmip.h
 	$(HOSTCXX) $(ASANFLAGS) $< -L$(ASAN_DIR) -ldmip_asan -Wl,-rpath,$(abspath $(ASAN_DIR)) -lpthread -o $@

@@ -6,6 +6,7 @@ SONAME libamdhip64.so.7; the dynamic loader then reuses torch's copy and device 
 streams are shared). There is no fallback: if the library is missing, every device entry point
 raises.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -76,23 +77,21 @@ class DmipScatNoise(ctypes.Structure):
 
 
 _c_void_p = ctypes.c_void_p
-_i32, _i64, _u64 = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
+_i32, _i64, _u64t = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
 _f32 = ctypes.c_float
 
 _lib = None
 _lock = threading.Lock()
-calls = {"em_sample": 0, "mlp_forward": 0, "em_sample_posterior": 0, "em_sample_cdiffe": 0, "loss_grad": 0}  # instrumentation: proves the HIP path ran
+calls = collections.Counter()  # instrumentation: proves the HIP path ran (calls of each wrapper below)
 
 
 def _declare(lib):
     lib.dmip_last_error.restype = ctypes.c_char_p
-    lib.dmip_abi_version.restype = _i32
     lib.dmip_sampler_supported.argtypes = [_i32, _i32, _i32, _i32, _i32]
     lib.dmip_sampler_supported_f32.argtypes = [_i32, _i32, _i32, _i32, _i32]
     lib.dmip_sampler_supported_precision.argtypes = [_i32, _i32, _i32, _i32, _i32, _i32]  # ABI >= 6 (EXPORTED)
-    lib.dmip_sampler_supported_precision.restype = _i32
     lib.dmip_device_status.argtypes = [_c_void_p]
-    lib.dmip_train_draws.argtypes = [_u64, _u64, _i64, _i32, _i32, ctypes.POINTER(DmipVpsde), ctypes.c_double, _f32,
+    lib.dmip_train_draws.argtypes = [_u64t, _u64t, _i64, _i32, _i32, ctypes.POINTER(DmipVpsde), ctypes.c_double, _f32,
                                      _c_void_p, _c_void_p, _c_void_p]
     lib.dmip_adam_step.argtypes = [_i32, ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
                                    ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64), ctypes.c_double, ctypes.c_double,
@@ -113,39 +112,34 @@ def _declare(lib):
     lib.dmip_mlp_forward.argtypes = [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i32, _i64,
                                      _c_void_p, _i32, _c_void_p]
     lib.dmip_em_sample.argtypes = [_c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32, _i32,
-                                   _i64, _i64, _i32, _f32, _f32, _u64, _i32, _c_void_p, _c_void_p,
+                                   _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _c_void_p, _c_void_p,
                                    _c_void_p]
     lib.dmip_em_sample_posterior.argtypes = [_c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32,
-                                             _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _c_void_p,
+                                             _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _c_void_p,
                                              _c_void_p]
     lib.dmip_em_sample_cdiffe.argtypes = [_c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32, _i32,
-                                          _i64, _i64, _i32, _f32, _f32, _u64, _i32, _i32, _f32, _c_void_p,
+                                          _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _i32, _f32, _c_void_p,
                                           _c_void_p]
     if hasattr(lib, "dmip_em_sample_snapshots"):  # (absent from older builds loaded by A/B timing scripts)
         lib.dmip_em_sample_snapshots.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32,
-                                                 _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _i32, _f32,
+                                                 _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _i32, _f32,
                                                  _i32, _c_void_p, _c_void_p, _c_void_p]
     if hasattr(lib, "dmip_em_sample_lmbd"):  # (absent from older builds loaded by A/B timing scripts)
         lib.dmip_em_sample_lmbd.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32,
-                                            _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, ctypes.c_double, _c_void_p,
+                                            _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, ctypes.c_double, _c_void_p,
                                             _i32, _c_void_p, _c_void_p, _c_void_p]
-        lib.dmip_em_sample_lmbd.restype = _i32
         lib.dmip_flow_logp.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p, _i32,
                                        _i32, _i32, _i64, _i32, _c_void_p, _c_void_p, _c_void_p]
-        lib.dmip_flow_logp.restype = _i32
         lib.dmip_flow_logp_supported.argtypes = [_i32, _i32, _i32, _i32, _i32]
-        lib.dmip_flow_logp_supported.restype = _i32
     if hasattr(lib, "dmip_ode_sample"):  # (absent from older builds loaded by A/B timing scripts)
         lib.dmip_ode_sample.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32,
-                                        _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _i32, _c_void_p, _i32,
+                                        _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _i32, _c_void_p, _i32,
                                         _c_void_p, _c_void_p, _c_void_p]
-        lib.dmip_ode_sample.restype = _i32
         lib.dmip_ode_sample_supported.argtypes = [_i32] * 7
-        lib.dmip_ode_sample_supported.restype = _i32
     if hasattr(lib, "dmip_train_plan_create"):
         lib.dmip_train_plan_create.argtypes = [ctypes.POINTER(DmipTrainPlanDesc), ctypes.POINTER(_c_void_p)]
         lib.dmip_train_plan_step.argtypes = [_c_void_p, _c_void_p, _c_void_p, _c_void_p]
-        lib.dmip_train_plan_set_counters.argtypes = [_c_void_p, _u64, _i64, _c_void_p]
+        lib.dmip_train_plan_set_counters.argtypes = [_c_void_p, _u64t, _i64, _c_void_p]
         lib.dmip_train_plan_destroy.argtypes = [_c_void_p]
     lib.dmip_loss_grad.argtypes = [_i32, _i32, _i32, ctypes.POINTER(_i32), _i32, ctypes.POINTER(_c_void_p),
                                    ctypes.POINTER(_c_void_p), ctypes.POINTER(DmipVpsde), ctypes.POINTER(DmipLossCfg),
@@ -155,9 +149,9 @@ def _declare(lib):
                                    _c_void_p]
     lib.dmip_loss_grad_supported.argtypes = [_i32, _i32, _i32, ctypes.POINTER(_i32), _i32]
     lib.dmip_em_sample_stamps.argtypes = [_c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32, _i32, _i32,
-                                          _i64, _i32, _u64, _c_void_p, _c_void_p, _c_void_p]
-    lib.dmip_rng_words.argtypes = [_u64, _i64, _u64, _i64, _i32, _c_void_p, _c_void_p]
-    lib.dmip_rng_normals.argtypes = [_u64, _i64, _u64, _i64, _i32, _c_void_p, _c_void_p]
+                                          _i64, _i32, _u64t, _c_void_p, _c_void_p, _c_void_p]
+    lib.dmip_rng_words.argtypes = [_u64t, _i64, _u64t, _i64, _i32, _c_void_p, _c_void_p]
+    lib.dmip_rng_normals.argtypes = [_u64t, _i64, _u64t, _i64, _i32, _c_void_p, _c_void_p]
     lib.dmip_schedule.argtypes = [_i32, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p]
     lib.dmip_surrogate_create.argtypes = [_i32, _i32, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_c_void_p),
                                           ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p)]
@@ -166,25 +160,20 @@ def _declare(lib):
     lib.dmip_log_posterior.argtypes = [_c_void_p, ctypes.POINTER(DmipScatNoise), _c_void_p, _c_void_p, _i64, _i64,
                                        _c_void_p, _c_void_p, _c_void_p]
     lib.dmip_mh_sample.argtypes = [_c_void_p, ctypes.POINTER(DmipScatNoise), _c_void_p, _i32, _i64, _i64, _i32, _f32,
-                                   _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
+                                   _u64t, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
     lib.dmip_dps_sample.argtypes = [_c_void_p, _c_void_p, ctypes.POINTER(DmipScatNoise), ctypes.POINTER(DmipVpsde),
-                                    _c_void_p, _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _f32, _c_void_p,
+                                    _c_void_p, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _f32, _c_void_p,
                                     _c_void_p]
     lib.dmip_dps_sample_ex.argtypes = [_c_void_p, _c_void_p, ctypes.POINTER(DmipScatNoise), ctypes.POINTER(DmipVpsde),
-                                       _c_void_p, _i32, _i64, _i64, _i32, _f32, _f32, _u64, _i32, _f32, _i32,
+                                       _c_void_p, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _f32, _i32,
                                        _c_void_p, _c_void_p]
-    lib.dmip_dps_sample_ex.restype = _i32
     if hasattr(lib, "dmip_mh_sample_ex"):  # ABI >= 9
         lib.dmip_mh_sample_ex.argtypes = [_c_void_p, ctypes.POINTER(DmipScatNoise), _c_void_p, _i32, _i64, _i64, _i32,
-                                          _f32, _u64, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                          _f32, _u64t, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                                           _c_void_p]
-        lib.dmip_mh_sample_ex.restype = _i32
-    for name in ("dmip_train_draws", "dmip_adam_step", "dmip_loss_grad_f32", "dmip_posterior_loss_grad", "dmip_device_status", "dmip_sampler_supported_f32", "dmip_dps_sample", "dmip_mlp_create", "dmip_mlp_destroy", "dmip_mlp_forward", "dmip_em_sample",
-                 "dmip_rng_words", "dmip_rng_normals", "dmip_schedule", "dmip_sampler_supported",
-                 "dmip_em_sample_stamps", "dmip_em_sample_posterior", "dmip_em_sample_cdiffe",
-                 "dmip_loss_grad", "dmip_loss_grad_supported", "dmip_histogram", "dmip_surrogate_create",
-                 "dmip_surrogate_destroy", "dmip_surrogate_forward", "dmip_log_posterior", "dmip_mh_sample"):
-        getattr(lib, name).restype = _i32
+    for name in EXPORTED:  # every entry point returns int but dmip_last_error
+        if name != "dmip_last_error" and hasattr(lib, name):
+            getattr(lib, name).restype = _i32
 
 
 class _OlderBuild:
@@ -246,6 +235,15 @@ def check(rc):
 
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def _u64(v):
+    return ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _h(handle):
+    """The dmip_mlp* of an optional MlpHandle (the Posterior prior; None elsewhere)."""
+    return handle.h if handle is not None else None
 
 
 def stream_of(device):
@@ -315,8 +313,7 @@ def em_sample(handle, sde, y, n_chains, chain_offset, num_steps, mean, std, seed
     _status_pending.add(_dev_index(y.device))
     n_y, ydim = y.shape
     check(lib().dmip_em_sample(handle.h, ctypes.byref(sde), ptr(y), n_y, ydim, handle.xdim,
-                               int(n_chains), int(chain_offset), int(num_steps), float(mean),
-                               float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std), _u64(seed),
                                precision_code(precision), ptr(noise), ptr(out), stream_of(y.device)))
 
 
@@ -327,8 +324,8 @@ def em_sample_posterior(prior, likelihood, sde, y, n_chains, chain_offset, num_s
     n_y, ydim = y.shape
     check(lib().dmip_em_sample_posterior(prior.h, likelihood.h, ctypes.byref(sde), ptr(y), n_y, ydim,
                                          likelihood.xdim, int(n_chains), int(chain_offset), int(num_steps),
-                                         float(mean), float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                         precision_code(precision), ptr(out), stream_of(y.device)))
+                                         float(mean), float(std), _u64(seed), precision_code(precision), ptr(out),
+                                         stream_of(y.device)))
 
 
 def em_sample_cdiffe(handle, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, out, corrector_steps=0,
@@ -338,37 +335,34 @@ def em_sample_cdiffe(handle, sde, y, n_chains, chain_offset, num_steps, mean, st
     n_y, ydim = y.shape
     check(lib().dmip_em_sample_cdiffe(handle.h, ctypes.byref(sde), ptr(y), n_y, ydim, handle.xdim,
                                       int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std),
-                                      ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), precision_code(precision),
-                                      int(corrector_steps), float(snr), ptr(out), stream_of(y.device)))
+                                      _u64(seed), precision_code(precision), int(corrector_steps), float(snr),
+                                      ptr(out), stream_of(y.device)))
 
 
 def em_sample_snapshots(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, snapshot_every,
                         snaps, out, corrector_steps=0, snr=0.16, precision="fp16"):
     """dmip_em_sample_snapshots: the fused sampler of `mode` that also writes x after every
     snapshot_every-th step into snaps [num_steps // snapshot_every][n_y][n_chains][xdim]."""
-    calls["em_sample_snapshots"] = calls.get("em_sample_snapshots", 0) + 1
+    calls["em_sample_snapshots"] += 1
     _status_pending.add(_dev_index(y.device))
     n_y, ydim = y.shape
-    check(lib().dmip_em_sample_snapshots(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde),
-                                         ptr(y), n_y, ydim, net.xdim, int(n_chains), int(chain_offset),
-                                         int(num_steps), float(mean), float(std),
-                                         ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), precision_code(precision),
-                                         int(corrector_steps), float(snr), int(snapshot_every), ptr(snaps), ptr(out),
-                                         stream_of(y.device)))
+    check(lib().dmip_em_sample_snapshots(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
+                                         int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std),
+                                         _u64(seed), precision_code(precision), int(corrector_steps), float(snr),
+                                         int(snapshot_every), ptr(snaps), ptr(out), stream_of(y.device)))
 
 
 def em_sample_lmbd(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, lmbd, out, noise=None,
                    snapshot_every=0, snaps=None, precision="fp16"):
     """dmip_em_sample_lmbd: the fused CDE / Posterior sampler of the lambda family (sdes.py:77-87; lmbd = 1 the
     probability-flow ODE), optionally with trajectory snapshots."""
-    calls["em_sample_lmbd"] = calls.get("em_sample_lmbd", 0) + 1
+    calls["em_sample_lmbd"] += 1
     _status_pending.add(_dev_index(y.device))
     n_y, ydim = y.shape
-    check(lib().dmip_em_sample_lmbd(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde), ptr(y),
-                                    n_y, ydim, net.xdim, int(n_chains), int(chain_offset), int(num_steps), float(mean),
-                                    float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                    precision_code(precision), float(lmbd), ptr(noise), int(snapshot_every), ptr(snaps),
-                                    ptr(out), stream_of(y.device)))
+    check(lib().dmip_em_sample_lmbd(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
+                                    int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std),
+                                    _u64(seed), precision_code(precision), float(lmbd), ptr(noise),
+                                    int(snapshot_every), ptr(snaps), ptr(out), stream_of(y.device)))
 
 
 def solver_code(solver):
@@ -386,14 +380,13 @@ def ode_sample(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean
                x0=None, snapshot_every=0, snaps=None, precision="fp32x3"):
     """dmip_ode_sample: the fused CDE / Posterior sampler of the probability-flow ODE; "heun" is the second-order
     solver (x0 (n_y, n_chains, xdim) replaces the chain's own start state), "euler" dmip_em_sample_lmbd at lmbd = 1."""
-    calls["ode_sample"] = calls.get("ode_sample", 0) + 1
+    calls["ode_sample"] += 1
     _status_pending.add(_dev_index(y.device))
     n_y, ydim = y.shape
-    check(lib().dmip_ode_sample(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde), ptr(y),
-                                n_y, ydim, net.xdim, int(n_chains), int(chain_offset), int(num_steps), float(mean),
-                                float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), precision_code(precision),
-                                solver_code(solver), ptr(x0), int(snapshot_every), ptr(snaps), ptr(out),
-                                stream_of(y.device)))
+    check(lib().dmip_ode_sample(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
+                                int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std), _u64(seed),
+                                precision_code(precision), solver_code(solver), ptr(x0), int(snapshot_every),
+                                ptr(snaps), ptr(out), stream_of(y.device)))
 
 
 def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE):
@@ -402,12 +395,11 @@ def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE):
 
 def flow_logp(mode, net, prior, sde, x, y, num_steps, logp, latent=None):
     """dmip_flow_logp: log p(x | y) of x (n_y, n, xdim) under ys (n_y, ydim) into logp (n_y, n) [and x_S into latent]."""
-    calls["flow_logp"] = calls.get("flow_logp", 0) + 1
+    calls["flow_logp"] += 1
     _status_pending.add(_dev_index(y.device))  # (parallel.guarded then reads the status word after the launch)
     n_y, ydim = y.shape
-    check(lib().dmip_flow_logp(int(mode), net.h, prior.h if prior is not None else None, ctypes.byref(sde), ptr(x),
-                               ptr(y), n_y, ydim, net.xdim, int(x.shape[1]), int(num_steps), ptr(logp), ptr(latent),
-                               stream_of(y.device)))
+    check(lib().dmip_flow_logp(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(x), ptr(y), n_y, ydim, net.xdim,
+                               int(x.shape[1]), int(num_steps), ptr(logp), ptr(latent), stream_of(y.device)))
 
 
 def sampler_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp16"):
@@ -454,9 +446,8 @@ def clear_range_status(device):
 
 def rng_normals(seed, chain_offset, stream_id, n_chains, n_pairs, out):
     """(n_chains, 2 n_pairs) standard normals of the kernels' chain-keyed generator (dmip_rng_normals)."""
-    check(lib().dmip_rng_normals(ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(chain_offset),
-                                 ctypes.c_uint64(int(stream_id) & 0xFFFFFFFFFFFFFFFF), int(n_chains), int(n_pairs),
-                                 ptr(out), stream_of(out.device)))
+    check(lib().dmip_rng_normals(_u64(seed), int(chain_offset), _u64(stream_id), int(n_chains), int(n_pairs), ptr(out),
+                                 stream_of(out.device)))
 
 
 def loss_grad_supported(in_dim, out_dim, widths, xdim):
@@ -478,7 +469,7 @@ def loss_grad(layers, in_dim, out_dim, xdim, sde, cfg, x, y, t, eps, grad_out, l
 
 def loss_grad_f32(layers, in_dim, out_dim, xdim, sde, cfg, x, y, t, eps, grad_out, loss_out, ic_target=None):
     """dmip_loss_grad_f32: the exact-f32 stacked-jet training step at any width."""
-    calls["loss_grad_f32"] = calls.get("loss_grad_f32", 0) + 1
+    calls["loss_grad_f32"] += 1
     L = len(layers) - 1
     widths = (_i32 * L)(*[int(layers[i][0].shape[0]) for i in range(L)])
     wp = (_c_void_p * (L + 1))(*[w.data_ptr() for w, _ in layers])
@@ -490,7 +481,7 @@ def loss_grad_f32(layers, in_dim, out_dim, xdim, sde, cfg, x, y, t, eps, grad_ou
 
 def histogram(x, nbins, lo, hi, counts):
     """x: (n_hist, n, d) fp32 device tensor; counts: (n_hist, nbins**d) int32 device tensor (accumulated)."""
-    calls["histogram"] = calls.get("histogram", 0) + 1
+    calls["histogram"] += 1
     n_hist, n, d = x.shape
     check(lib().dmip_histogram(ptr(x), int(n), int(d), int(nbins), float(lo), float(hi), int(n_hist), ptr(counts),
                                stream_of(x.device)))
@@ -529,12 +520,12 @@ def scat_noise(a, b, lambd_bd):
 
 
 def surrogate_forward(handle, x, out):
-    calls["surrogate_forward"] = calls.get("surrogate_forward", 0) + 1
+    calls["surrogate_forward"] += 1
     check(lib().dmip_surrogate_forward(handle.h, ptr(x), int(x.shape[0]), ptr(out), stream_of(x.device)))
 
 
 def log_posterior(handle, noise, x, y, y_stride, e_out, grad_out=None):
-    calls["log_posterior"] = calls.get("log_posterior", 0) + 1
+    calls["log_posterior"] += 1
     check(lib().dmip_log_posterior(handle.h, ctypes.byref(noise), ptr(x), ptr(y), int(y_stride), int(x.shape[0]),
                                    ptr(e_out), ptr(grad_out), stream_of(x.device)))
 
@@ -542,24 +533,23 @@ def log_posterior(handle, noise, x, y, y_stride, e_out, grad_out=None):
 def mh_sample(handle, noise, y, n_chains, chain_offset, num_steps, noise_std, seed, x_out, x_init=None,
               inj_noise=None, inj_unif=None, e_out=None, precision="fp32"):
     """dmip_mh_sample_ex: "fp32" the exact-f32 kernel, "fp32x3" the split-fp16 one (dmip_dps_x3.hip mh_x3_kernel)."""
-    calls["mh_sample"] = calls.get("mh_sample", 0) + 1
+    calls["mh_sample"] += 1
     _status_pending.add(_dev_index(y.device))
     check(lib().dmip_mh_sample_ex(handle.h, ctypes.byref(noise), ptr(y), int(y.shape[0]), int(n_chains),
-                                  int(chain_offset), int(num_steps), float(noise_std),
-                                  ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ptr(x_init), ptr(inj_noise),
-                                  ptr(inj_unif), precision_code(precision), ptr(x_out), ptr(e_out),
+                                  int(chain_offset), int(num_steps), float(noise_std), _u64(seed), ptr(x_init),
+                                  ptr(inj_noise), ptr(inj_unif), precision_code(precision), ptr(x_out), ptr(e_out),
                                   stream_of(y.device)))
 
 
 def dps_sample(prior, surrogate, noise, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, mode, zeta, out,
                precision="fp32"):
     """dmip_dps_sample_ex: "fp32" the exact-f32 kernel, "fp32x3" the split-fp16 one (dmip_dps_x3.hip)."""
-    calls["dps_sample"] = calls.get("dps_sample", 0) + 1
+    calls["dps_sample"] += 1
     _status_pending.add(_dev_index(y.device))
     check(lib().dmip_dps_sample_ex(prior.h, surrogate.h, ctypes.byref(noise), ctypes.byref(sde), ptr(y),
                                    int(y.shape[0]), int(n_chains), int(chain_offset), int(num_steps), float(mean),
-                                   float(std), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(mode), float(zeta),
-                                   precision_code(precision), ptr(out), stream_of(y.device)))
+                                   float(std), _u64(seed), int(mode), float(zeta), precision_code(precision), ptr(out),
+                                   stream_of(y.device)))
 
 
 def posterior_loss_grad(prior_layers, lik_layers, surrogate, noise, lam, sde, x, y, t, eps, grad_prior, grad_lik,
@@ -567,7 +557,7 @@ def posterior_loss_grad(prior_layers, lik_layers, surrogate, noise, lam, sde, x,
     """dmip_posterior_loss_grad (A18): layers = [(weight, bias)] device fp32 tensors of the prior (MLP2) and
     likelihood (MLP) networks; writes the flat reference-order gradients, loss_out[3] and optionally the
     likelihood target."""
-    calls["posterior_loss_grad"] = calls.get("posterior_loss_grad", 0) + 1
+    calls["posterior_loss_grad"] += 1
     L = len(prior_layers) - 1
     widths = (_i32 * L)(*[int(prior_layers[i][0].shape[0]) for i in range(L)])
     arr = lambda ts: (_c_void_p * (L + 1))(*[v.data_ptr() for v in ts])

@@ -112,34 +112,52 @@ def _x0_tensor(x0, ys, num_samples, xdim, dev):
     return x0.contiguous()
 
 
-def _heun_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,)):
-    """_fused_precision for solver="heun": fp32x3 (the one-tile engine) or fp32; "fp16" runs fp32x3 (there is no
-    16-bit Heun kernel). None: the per-step loop."""
-    _lib.precision_code(precision)
-    precision = canonical_precision(precision)
-    if any(a != _lib.DMIP_ACT_TANH_TWICE_FIRST for a in acts):
-        # (the SiLU chain's Heun kernel: every shape of its exact-f32 CDE sampler)
-        ok = mode == _lib.DMIP_SAMPLER_CDE and _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, "fp32")
-        return "fp32" if ok else None
-    for prec in (precision,) + _MORE_ACCURATE[precision]:
-        if _lib.ode_sample_supported(width, n_hidden, xdim, ydim, mode, prec):
-            return prec
-    return None
-
-
-def _fused_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,)):
+def _fused_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,),
+                     solver="euler"):
     """The precision a fused kernel runs this shape in: the requested one, else the next more accurate
     one that is compiled (_MORE_ACCURATE); None when none is (per-step loop). `acts`: the networks' activation
-    chains -- a SiLU network has the exact-f32 CDE sampler only (include/dmip.h dmip_act)."""
+    chains -- a SiLU network has the exact-f32 CDE sampler only (include/dmip.h dmip_act), and its Heun kernel at
+    every shape of that sampler. solver="heun": fp32x3 (the one-tile engine) or fp32; "fp16" runs fp32x3 (there is
+    no 16-bit Heun kernel)."""
     _lib.precision_code(precision)
     precision = canonical_precision(precision)
     if any(a != _lib.DMIP_ACT_TANH_TWICE_FIRST for a in acts):
         ok = mode == _lib.DMIP_SAMPLER_CDE and _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, "fp32")
         return "fp32" if ok else None
     for prec in (precision,) + _MORE_ACCURATE[precision]:
-        if _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, prec):
+        if _lib.ode_sample_supported(width, n_hidden, xdim, ydim, mode, prec) if solver == "heun" else \
+                _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, prec):
             return prec
     return None
+
+
+def _nets_and_mode(model, error, cdiffe=False):
+    """(networks, sampler mode) of a model with a fused kernel: [prior, likelihood] for the Posterior estimator, the
+    score network for CDE (and CDiffE where the caller has a kernel for it); raises `error` for any other model."""
+    if isinstance(model, PosteriorDiffusionEstimator):
+        return [model.sde.a.prior_net, model.sde.a.likelihood_net], _lib.DMIP_SAMPLER_POSTERIOR
+    if isinstance(model, CDE):
+        return [model.sde.a], _lib.DMIP_SAMPLER_CDE
+    if cdiffe and isinstance(model, CDiffE):
+        return [model.sde.a], _lib.DMIP_SAMPLER_CDIFFE
+    raise error
+
+
+def _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec,
+                  lmbd=0.0, solver="euler", x0=None, noise=None):
+    """The fused CDE / Posterior launch of sample_device: dmip_ode_sample for Heun, dmip_em_sample_lmbd for
+    lmbd != 0, else the reverse SDE's own entry point (dmip_em_sample / dmip_em_sample_posterior)."""
+    if solver == "heun":
+        _lib.ode_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, "heun",
+                        x0, precision=prec)
+    elif lmbd != 0.0:
+        _lib.em_sample_lmbd(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, lmbd,
+                            out, noise, precision=prec)
+    elif mode == _lib.DMIP_SAMPLER_POSTERIOR:
+        _lib.em_sample_posterior(prior, net, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec)
+    else:
+        _lib.em_sample(net, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, noise, prec)
+    return out
 
 
 class BaseClassDiffusionModel:
@@ -183,14 +201,8 @@ class BaseClassDiffusionModel:
         forward (dmip_em_sample_lmbd with snapshots); `solver="heun"`: the states after each full Heun step
         (dmip_ode_sample)."""
         lmbd = _check_solver(solver, lmbd, self)
-        if isinstance(self, PosteriorDiffusionEstimator):
-            score = self.sde.a
-            nets, mode = [score.prior_net, score.likelihood_net], _lib.DMIP_SAMPLER_POSTERIOR
-        elif isinstance(self, (CDE, CDiffE)):
-            nets = [self.sde.a]
-            mode = _lib.DMIP_SAMPLER_CDIFFE if isinstance(self, CDiffE) else _lib.DMIP_SAMPLER_CDE
-        else:
-            raise NotImplementedError(f"{type(self).__name__}: no fused trajectory sampler")
+        nets, mode = _nets_and_mode(self, NotImplementedError(f"{type(self).__name__}: no fused trajectory sampler"),
+                                    cdiffe=True)
         if corrector_steps and mode != _lib.DMIP_SAMPLER_CDIFFE:
             raise ValueError("corrector steps: CDiffE only")
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, nets)
@@ -198,8 +210,8 @@ class BaseClassDiffusionModel:
         net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
         if prior is not None and (prior.width, prior.n_hidden) != (net.width, net.n_hidden):
             raise ValueError("prior and likelihood networks must have the same hidden layers")
-        prec = (_heun_precision if solver == "heun" else _fused_precision)(
-            precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim, [h.act for h in handles])
+        prec = _fused_precision(precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim,
+                                [h.act for h in handles], solver)
         if prec is None:
             raise ValueError("no fused sampler for this network shape / activation")
         snaps = torch.empty(int(num_steps) // int(snapshot_every), ys.shape[0], int(num_samples), self.xdim,
@@ -229,14 +241,8 @@ class BaseClassDiffusionModel:
         (n_y, ydim) -> (n_y, n). return_latent=True: (logp, x_S), x_S shaped as x. CDE and
         PosteriorDiffusionEstimator; like sampling there is no CPU path, and a shape or activation without a
         compiled kernel raises ValueError."""
-        if isinstance(self, PosteriorDiffusionEstimator):
-            score = self.sde.a
-            nets, mode = [score.prior_net, score.likelihood_net], _lib.DMIP_SAMPLER_POSTERIOR
-        elif isinstance(self, CDE):
-            nets, mode = [self.sde.a], _lib.DMIP_SAMPLER_CDE
-        else:
-            raise ValueError(f"{type(self).__name__}: log_prob is implemented for CDE and PosteriorDiffusionEstimator "
-                             "only")
+        nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: log_prob is implemented for CDE and "
+                                                     "PosteriorDiffusionEstimator only"))
         layers = [list(n.hidden_layers) for n in nets]
         widths = set(w for hl in layers for w in hl)
         if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
@@ -360,9 +366,8 @@ class CDE(BaseClassDiffusionModel):
         handle = net.dmip_handle(dev, self.xdim)
         seed = _draw_seed() if seed is None else seed
         x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
-        prec = (_heun_precision if solver == "heun" else _fused_precision)(
-            precision or self.precision, _lib.DMIP_SAMPLER_CDE, handle.width, handle.n_hidden, self.xdim, self.ydim,
-            [handle.act])
+        prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_CDE, handle.width, handle.n_hidden,
+                                self.xdim, self.ydim, [handle.act], solver)
         if noise is not None:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
             if tuple(noise.shape) != (int(num_steps) + 1, ys.shape[0], int(num_samples), self.xdim):
@@ -377,16 +382,8 @@ class CDE(BaseClassDiffusionModel):
 
             return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
                                    drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
-        if solver == "heun":
-            _lib.ode_sample(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps, mean,
-                            std, seed, out, "heun", x0, precision=prec)
-            return out
-        if lmbd != 0.0:
-            _lib.em_sample_lmbd(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps,
-                                mean, std, seed, lmbd, out, noise, precision=prec)
-            return out
-        _lib.em_sample(handle, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, noise, prec)
-        return out
+        return _fused_launch(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps, mean,
+                             std, seed, out, prec, lmbd, solver, x0, noise)
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         from .training import DeviceTrainStep, _plain_adam, device_step_enabled, device_step_ok, fused_config, \
@@ -574,21 +571,11 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         prec = None
         x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
         if (prior.width, prior.n_hidden) == (lik.width, lik.n_hidden):
-            prec = (_heun_precision if solver == "heun" else _fused_precision)(
-                precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width, lik.n_hidden, self.xdim,
-                self.ydim, [prior.act, lik.act])
-        if prec is not None and solver == "heun":
-            _lib.ode_sample(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset, num_steps,
-                            mean, std, seed, out, "heun", x0, precision=prec)
-            return out
-        if prec is not None and lmbd != 0.0:
-            _lib.em_sample_lmbd(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset, num_steps,
-                                mean, std, seed, lmbd, out, precision=prec)
-            return out
+            prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width, lik.n_hidden,
+                                    self.xdim, self.ydim, [prior.act, lik.act], solver)
         if prec is not None:
-            _lib.em_sample_posterior(prior, lik, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed,
-                                     out, prec)
-            return out
+            return _fused_launch(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset,
+                                 num_steps, mean, std, seed, out, prec, lmbd, solver, x0)
         base = self.sde.base_sde
 
         def drift(x, y, tvec):

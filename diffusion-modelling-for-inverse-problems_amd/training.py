@@ -354,7 +354,7 @@ class DeviceTrainStep:
             if self.ic_fn is not None:
                 with torch.enable_grad():
                     ic = self.ic_fn(x.clone(), y).detach()[:, :self.model.xdim].contiguous()
-            _lib.calls["loss_grad_f32"] = _lib.calls.get("loss_grad_f32", 0) + 1
+            _lib.calls["loss_grad_f32"] += 1
             _lib.check(lib.dmip_loss_grad_f32(self.net.input_dim, self.net.output_dim, L, self.widths,
                                               self.model.xdim, self.wp, self.bp, ctypes.byref(self.sde),
                                               ctypes.byref(self.cfg), P(x), P(y), P(self.t), P(self.eps), P(ic),
@@ -388,7 +388,7 @@ class DeviceTrainStep:
             _lib.check(self.lib.dmip_train_plan_set_counters(plan.h, self.k, step, self.stream))
         x = x.detach().to(device=self.dev, dtype=torch.float32).contiguous()
         y = y.detach().to(device=self.dev, dtype=torch.float32).contiguous()
-        _lib.calls["train_plan_step"] = _lib.calls.get("train_plan_step", 0) + 1
+        _lib.calls["train_plan_step"] += 1
         _lib.check(self.lib.dmip_train_plan_step(plan.h, self.ptr(x), self.ptr(y), self.stream))
         self.k += 1
         plan.k, plan.step = self.k, step + 1

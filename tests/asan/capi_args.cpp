@@ -3,6 +3,8 @@
 // arguments -- the paths that return before any device work -- plus the error-string plumbing, so
 // ASan sees the validation code's reads of caller arrays (widths, weight tables) and the
 // thread-local error buffer. Exits 0 when every call returned the documented status.
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -19,8 +21,167 @@ static void expect(int got, int want, const char* what) {
   }
 }
 
+// the status and dmip_last_error's text of a refusal
+static void refused(int got, int want, const char* msg, const char* what) {
+  if (got != want || std::strcmp(dmip_last_error(), msg) != 0) {
+    std::printf("FAIL %s: status %d, want %d; message '%s', want '%s'\n", what, got, want, dmip_last_error(), msg);
+    ++failures;
+  }
+}
+
+// The sampler, flow, DPS and MH entry points' refusals that need no handle, in the order each entry point checks
+// (where two arguments are wrong, the first check's message).
+static void sampler_refusals() {
+  const dmip_vpsde sde{0.1, 20.0, 1.0};
+  const dmip_scat_noise nz{0.2f, 0.01f, 1000.f}, nz_bad{0.2f, 0.0f, 1000.f};
+  float buf[4] = {};
+  uint64_t stamps[4] = {};
+  const int INV = DMIP_ERR_INVALID, UNS = DMIP_ERR_UNSUPPORTED;
+  const int CDE = DMIP_SAMPLER_CDE, POST = DMIP_SAMPLER_POSTERIOR, CDIFFE = DMIP_SAMPLER_CDIFFE;
+  const char* null_arg = "null argument";
+  const char* snap01 = "snapshot_every must be 0 or in [1, num_steps] with a snapshot buffer";
+  // dmip_em_sample*, every null in turn
+  refused(dmip_em_sample(nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, nullptr, buf, nullptr), INV, null_arg,
+          "em_sample: null net");
+  refused(dmip_em_sample(nullptr, nullptr, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 7, nullptr, buf, nullptr), INV,
+          null_arg, "em_sample: null before precision");
+  refused(dmip_em_sample_posterior(nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 1, buf, nullptr), INV,
+          null_arg, "posterior: null prior");
+  refused(dmip_em_sample_cdiffe(nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, -1, 0.f, buf, nullptr), INV,
+          "corrector_steps must be >= 0", "cdiffe: corrector before snr");
+  refused(dmip_em_sample_cdiffe(nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1, 0.f, buf, nullptr), INV,
+          "snr must be > 0", "cdiffe: snr");
+  refused(dmip_em_sample_cdiffe(nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1, 0.16f, buf, nullptr), INV,
+          null_arg, "cdiffe: null net");
+  refused(dmip_em_sample_stamps(nullptr, &sde, buf, 1, 2, 2, 10, 10, 1, buf, nullptr, nullptr), INV,
+          "null stamps buffer", "stamps: null buffer");
+  refused(dmip_em_sample_stamps(nullptr, &sde, buf, 1, 2, 2, 10, 10, 1, buf, stamps, nullptr), INV, null_arg,
+          "stamps: null net");
+  // dmip_em_sample_snapshots
+  refused(dmip_em_sample_snapshots(7, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 0, 0.16f, 0,
+                                   nullptr, buf, nullptr),
+          INV, "unknown sampler mode", "snapshots: mode before snapshot_every");
+  for (int every : {0, 11})
+    refused(dmip_em_sample_snapshots(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 0, 0.16f,
+                                     every, nullptr, buf, nullptr),
+            INV, "snapshot_every must be in [1, num_steps]", "snapshots: every before null buffer");
+  refused(dmip_em_sample_snapshots(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 0, 0.16f, 2,
+                                   nullptr, buf, nullptr),
+          INV, "null snapshot buffer", "snapshots: null buffer");
+  refused(dmip_em_sample_snapshots(POST, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1, 0.16f, 2,
+                                   buf, buf, nullptr),
+          INV, null_arg, "snapshots: null prior before corrector");
+  refused(dmip_em_sample_snapshots(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1, 0.16f, 2,
+                                   buf, buf, nullptr),
+          INV, "corrector steps: CDiffE sampler only", "snapshots: corrector, CDE");
+  refused(dmip_em_sample_snapshots(CDIFFE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, -1, 0.f, 2,
+                                   buf, buf, nullptr),
+          INV, "corrector_steps must be >= 0", "snapshots: corrector < 0");
+  refused(dmip_em_sample_snapshots(CDIFFE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1, 0.f, 2,
+                                   buf, buf, nullptr),
+          INV, "snr must be > 0", "snapshots: snr");
+  refused(dmip_em_sample_snapshots(CDIFFE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1, 0.16f,
+                                   2, buf, buf, nullptr),
+          INV, null_arg, "snapshots: null net");
+  // dmip_em_sample_lmbd
+  refused(dmip_em_sample_lmbd(CDIFFE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1.5, nullptr, 0,
+                              nullptr, buf, nullptr),
+          INV, "em_sample_lmbd: CDE and Posterior samplers only", "lmbd: mode before lmbd");
+  refused(dmip_em_sample_lmbd(POST, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1.5, nullptr, 0,
+                              nullptr, buf, nullptr),
+          INV, null_arg, "lmbd: null prior before lmbd");
+  for (double l : {1.5, -0.25, std::nan("")})
+    refused(dmip_em_sample_lmbd(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 0, 0.f, 1.f, 1, 0, l, nullptr, 0,
+                                nullptr, buf, nullptr),
+            INV, "lmbd must be in [0, 1]", "lmbd: lmbd before num_steps");
+  refused(dmip_em_sample_lmbd(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 0, 0.f, 1.f, 1, 0, 1.0, nullptr, -1,
+                              nullptr, buf, nullptr),
+          INV, "num_steps must be >= 1", "lmbd: num_steps before snapshot_every");
+  refused(dmip_em_sample_lmbd(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1.0, nullptr, -1,
+                              buf, buf, nullptr),
+          INV, snap01, "lmbd: snapshot_every < 0");
+  refused(dmip_em_sample_lmbd(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1.0, nullptr, 11,
+                              buf, buf, nullptr),
+          INV, snap01, "lmbd: snapshot_every > num_steps");
+  refused(dmip_em_sample_lmbd(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1.0, nullptr, 2,
+                              nullptr, buf, nullptr),
+          INV, snap01, "lmbd: snapshots without a buffer");
+  refused(dmip_em_sample_lmbd(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 0, 1.0, nullptr, 2,
+                              buf, buf, nullptr),
+          INV, null_arg, "lmbd: null net");
+  // dmip_ode_sample
+  const char* x0_euler =
+      "ode_sample: x0_dev needs DMIP_SOLVER_HEUN (the Euler samplers start from "
+      "injected noise: dmip_em_sample_lmbd's noise_dev)";
+  refused(dmip_ode_sample(CDIFFE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 2, 7, nullptr, 0,
+                          nullptr, buf, nullptr),
+          INV, "ode_sample: CDE and Posterior samplers only", "ode: mode before solver");
+  refused(dmip_ode_sample(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 0, 0.f, 1.f, 1, 2, 7, buf, 0, nullptr, buf,
+                          nullptr),
+          INV, "unknown solver", "ode: solver before num_steps");
+  refused(dmip_ode_sample(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 0, 0.f, 1.f, 1, 2, DMIP_SOLVER_HEUN,
+                          nullptr, 11, buf, buf, nullptr),
+          INV, "num_steps must be >= 1", "ode: num_steps before snapshot_every");
+  for (int solver : {DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN}) {
+    refused(dmip_ode_sample(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 2, solver, buf, 11, buf,
+                            buf, nullptr),
+            INV, snap01, "ode: snapshot_every before x0");
+    refused(dmip_ode_sample(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 2, solver, nullptr, 2,
+                            nullptr, buf, nullptr),
+            INV, snap01, "ode: snapshots without a buffer");
+    refused(dmip_ode_sample(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 2, solver, nullptr, 0,
+                            nullptr, buf, nullptr),
+            INV, null_arg, "ode: null net");
+    refused(dmip_ode_sample(POST, nullptr, nullptr, nullptr, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 2, solver, nullptr,
+                            0, nullptr, nullptr, nullptr),
+            INV, null_arg, "ode: nulls, Posterior");
+  }
+  refused(dmip_ode_sample(CDE, nullptr, nullptr, &sde, buf, 1, 2, 2, 10, 0, 10, 0.f, 1.f, 1, 2, DMIP_SOLVER_EULER, buf,
+                          0, nullptr, buf, nullptr),
+          UNS, x0_euler, "ode: x0 with Euler before null net");
+  expect(dmip_ode_sample_supported(CDIFFE, 64, 3, 2, 2, DMIP_PREC_F32, DMIP_SOLVER_HEUN), 0, "ode_supported: CDiffE");
+  expect(dmip_ode_sample_supported(CDE, 64, 3, 2, 2, DMIP_PREC_FP16, DMIP_SOLVER_HEUN), 0, "ode_supported: 16-bit Heun");
+  expect(dmip_ode_sample_supported(CDE, 64, 3, 2, 2, DMIP_PREC_F32, 7), 0, "ode_supported: solver");
+  expect(dmip_ode_sample_supported(CDE, 64, 3, 2, 2, DMIP_PREC_FP16, DMIP_SOLVER_EULER),
+         dmip_sampler_supported_precision(DMIP_PREC_FP16, CDE, 64, 3, 2, 2), "ode_supported: Euler");
+  expect(dmip_sampler_supported_precision(7, CDE, 64, 3, 2, 2), 0, "supported: precision");
+  // dmip_flow_logp
+  refused(dmip_flow_logp(CDIFFE, nullptr, nullptr, &sde, buf, buf, 1, 2, 2, 4, 0, buf, nullptr, nullptr), INV,
+          "flow_logp: CDE and Posterior estimators only", "flow: mode before num_steps");
+  refused(dmip_flow_logp(CDE, nullptr, nullptr, &sde, buf, buf, 1, 2, 2, 4, 0, buf, nullptr, nullptr), INV,
+          "num_steps must be >= 1", "flow: num_steps before null net");
+  refused(dmip_flow_logp(CDE, nullptr, nullptr, &sde, buf, buf, 1, 2, 2, 4, 8, buf, nullptr, nullptr), INV, null_arg,
+          "flow: null net");
+  refused(dmip_flow_logp(POST, nullptr, nullptr, &sde, buf, buf, 1, 2, 2, 4, 8, nullptr, nullptr, nullptr), INV,
+          null_arg, "flow: null prior / output");
+  // MH
+  refused(dmip_surrogate_forward(nullptr, buf, 4, buf, nullptr), INV, "null surrogate handle", "surrogate_forward: null");
+  refused(dmip_log_posterior(nullptr, &nz_bad, buf, buf, 5, -1, buf, nullptr, nullptr), INV, "null surrogate handle",
+          "log_posterior: handle first");
+  refused(dmip_mh_sample(nullptr, &nz_bad, nullptr, 0, -1, -1, -1, -1.f, 1, nullptr, buf, nullptr, nullptr, nullptr,
+                         nullptr),
+          INV, "null surrogate handle", "mh: handle first");
+  for (int prec : {DMIP_PREC_F32, DMIP_PREC_F32X3})
+    refused(dmip_mh_sample_ex(nullptr, &nz, buf, 1, 10, 0, 5, 0.5f, 1, nullptr, nullptr, nullptr, prec, buf, nullptr,
+                              nullptr),
+            INV, "null surrogate handle", "mh_ex: null handle");
+  refused(dmip_mh_sample_ex(nullptr, nullptr, nullptr, 0, 10, 0, 5, 0.5f, 1, nullptr, nullptr, nullptr, DMIP_PREC_FP16,
+                            nullptr, nullptr, nullptr),
+          INV, "MH precision: DMIP_PREC_F32 or DMIP_PREC_F32X3", "mh_ex: precision first");
+  // DPS
+  refused(dmip_dps_sample(nullptr, nullptr, &nz_bad, &sde, buf, 0, -1, 0, 0, 0.f, 1.f, 1, 7, -1.f, buf, nullptr), INV,
+          null_arg, "dps: null first");
+  for (int prec : {DMIP_PREC_F32, DMIP_PREC_F32X3})
+    refused(dmip_dps_sample_ex(nullptr, nullptr, &nz, &sde, buf, 1, 10, 0, 5, 0.f, 1.f, 1, 7, 1.f, prec, buf, nullptr),
+            INV, null_arg, "dps_ex: null before mode");
+  refused(dmip_dps_sample_ex(nullptr, nullptr, &nz, &sde, buf, 1, 10, 0, 5, 0.f, 1.f, 1, 0, 1.f, DMIP_PREC_FP16, buf,
+                             nullptr),
+          INV, "DPS precision: DMIP_PREC_F32 or DMIP_PREC_F32X3", "dps_ex: precision first");
+}
+
 int main() {
   expect(dmip_abi_version(), DMIP_ABI_VERSION, "abi version");
+  sampler_refusals();
   const int w3[3] = {64, 64, 64}, wneq[3] = {64, 32, 64}, w1[1] = {96};
   const float* null4[4] = {nullptr, nullptr, nullptr, nullptr};
   dmip_mlp* net = nullptr;

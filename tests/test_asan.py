@@ -1,5 +1,5 @@
 """Host-side AddressSanitizer run of the C-ABI layer (SURVEY.md §5 "Race detection / sanitizers"):
-`make asan` builds dmip_capi.cpp with -fsanitize=address (host code only; GPU sanitizers are not
+`make asan` builds the dmip_capi_*.cpp sources with -fsanitize=address (host code only; GPU sanitizers are not
 available on this pool), links it with the regular kernel objects, and tests/asan/capi_args.cpp drives
 every entry point's argument validation and the thread-local error buffer. CPU only."""
 import os
