@@ -5,7 +5,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-parameter
 F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(CSRC)/dmip_f32_cdiffe.o $(CSRC)/dmip_flow.o \
-           $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o
+           $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o
 # the C-ABI layer by concern: packers and handles, sampling entry points, training entry points
@@ -47,7 +47,11 @@ $(CSRC)/dmip_f32_%.o: $(CSRC)/dmip_f32_%.hip $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # log p(x | y) along the probability-flow ODE, on the exact-f32 engine's header
-$(CSRC)/dmip_flow.o: $(CSRC)/dmip_flow.hip $(CSRC)/dmip_f32.h $(HDRS)
+$(CSRC)/dmip_flow.o: $(CSRC)/dmip_flow.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_f32.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# samples with their log-density: the Heun sampler's steps with the log-likelihood kernel's tangent columns
+$(CSRC)/dmip_flow_sample.o: $(CSRC)/dmip_flow_sample.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # fp32-accurate split-fp16 engine (DMIP_PREC_F32X3): one header, four translation units; no SLP

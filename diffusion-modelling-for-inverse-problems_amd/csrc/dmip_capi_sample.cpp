@@ -517,6 +517,57 @@ int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const d
   return DMIP_OK;
 }
 
+int dmip_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
+  return dmip::f32_flow_sample_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+}
+
+// samples of the probability-flow ODE with their log-density (dmip_flow_sample.hip); every argument is validated
+// before any device work
+int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                     int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                     float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev, float* logq_out_dev,
+                     void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "flow_sample: CDE and Posterior estimators only");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (n_chains < 1) return fail(DMIP_ERR_INVALID, "n_chains must be >= 1");
+  if (!(stdv > 0.0f)) return fail(DMIP_ERR_INVALID, "stdv must be > 0");
+  if (!net || !sde || !y_dev || !x_out_dev || !logq_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
+    return fail(DMIP_ERR_INVALID, "null argument");
+  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
+  if (int rc = check_nets("flow_sample", net, net1, xdim, xdim, ydim, n_y, false, n_chains, chain_offset, num_steps,
+                          sde))
+    return rc;
+  if (f32_act(net) || (net1 && f32_act(net1)))
+    return fail(DMIP_ERR_UNSUPPORTED, "flow_sample: the tanh chain only (no SiLU kernel)");
+  if (!dmip::f32_flow_sample_supported(mode, net->width, net->n_hidden, xdim, ydim))
+    return no_kernel("flow_sample kernel", mode, net, xdim);
+  hipStream_t st = (hipStream_t)stream;
+  dmip::F32FlowSampleParams p{};
+  p.net[0] = f32_net(net);
+  if (net1) p.net[1] = f32_net(net1);
+  p.n_hidden = net->n_hidden;
+  StreamScratch l1y;
+  if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
+  p.l1y = (float*)l1y.ptr;
+  p.x0 = x0_dev;
+  p.x_out = x_out_dev;
+  p.logq = logq_out_dev;
+  p.n = n_chains;
+  p.chain_offset = chain_offset;
+  p.num_steps = num_steps;
+  fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.delta);
+  p.mean = mean;
+  p.stdv = stdv;
+  p.seed = seed;
+  p.base = -0.5 * (double)xdim * 1.8378770664093453 - (double)xdim * std::log((double)stdv);  // log 2 pi
+  bool ok = false;
+  const hipError_t e = dmip::launch_f32_flow_sample(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled flow_sample kernel");
+  if (e != hipSuccess) return hip_fail(e, "flow_sample launch");
+  return DMIP_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------- scatterometry surrogate: forward, MH, DPS

@@ -317,6 +317,25 @@ hipError_t launch_f32_flow(const F32FlowParams& p, int mode, int width, int n_hi
                            hipStream_t st, bool* supported);
 bool f32_flow_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 
+// samples with their log-density (dmip_flow_sample.hip): the Heun sampler's steps on the reverse grid and, beside
+// them, the divergence of the drift from forward tangents (the columns of the log-likelihood kernel)
+struct F32FlowSampleParams {
+  F32Net net[2];              // net 0: CDE / likelihood; net 1: the Posterior prior
+  const float* l1y;           // per-y layer-1 images [n_y][W/16][K1Q][64] (y folded in)
+  int n_hidden;
+  const float* x0;            // start states [n_y][n][D] or null (randn stdv + mean from the RNG)
+  float* x_out;               // [n_y][n][D]
+  float* logq;                // [n_y][n]
+  long long n, chain_offset;  // chains per y; the RNG's chain index of row 0
+  int num_steps;
+  float T, bmin, bdiff, delta, mean, stdv;
+  unsigned long long seed;
+  double base;                // -(D/2) log 2 pi - D log stdv
+};
+hipError_t launch_f32_flow_sample(const F32FlowSampleParams& p, int mode, int width, int n_hidden, int xdim, int ydim,
+                                  int n_y, hipStream_t st, bool* supported);
+bool f32_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim);
+
 hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, int n_hidden, int xdim, int ydim,
                               int n_y, hipStream_t st, bool* supported);
 bool f32_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim);

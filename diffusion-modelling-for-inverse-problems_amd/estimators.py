@@ -10,7 +10,8 @@ reverse-SDE kernel for all num_steps, the chain state never leaving the register
 CDE and PosteriorDiffusionEstimator sample the whole lambda family of the reference's PluginReverseSDE
 (sdes.py:77-87) with `lmbd=`: 0 the reverse SDE (the default), 1 the deterministic probability-flow ODE
 (dmip_em_sample_lmbd), and `model.log_prob(x, y)` is the model's own log-density log p(x | y) along that ODE
-(dmip_flow_logp, exact f32).
+(dmip_flow_logp, exact f32); `model.sample_with_log_prob(y, n)` draws samples of that ODE together with their
+log-density in one launch (dmip_flow_sample, exact f32).
 Precision (`model.precision`, or `precision=` per call; default from $DMIP_PRECISION, else "fp32x3"):
   "fp32x3" -- the reference's fp32 arithmetic at the fp16 matrix rate: every product as three fp16 MFMAs
              (W_hi h_hi + W_hi h_lo + W_lo h_hi, fp32 accumulation; csrc/dmip_x3.h), tanh by exp2 + rcp.
@@ -268,6 +269,49 @@ class BaseClassDiffusionModel:
         if single:
             logp, latent = logp[0], (latent[0] if return_latent else None)
         return (logp, latent) if return_latent else logp
+
+    def sample_with_log_prob(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, x0=None):
+        """Samples x ~ q(. | y) of the probability-flow ODE together with their model log-density log q(x | y), in
+        exact f32 in one launch (dmip_flow_sample): the steps of sample_device(solver="heun", precision="fp32") --
+        the same x at the same seed -- with the divergence of the drift (exact, forward tangents) integrated beside
+        them on the same grid, so the pair is consistent by construction (log_prob re-integrates on the forward grid
+        and agrees to second order in 1 / num_steps). Device tensors (x (n_y, num_samples, xdim), logq (n_y,
+        num_samples)) for ys (n_y, ydim); ((num_samples, xdim), (num_samples,)) for one y (ydim,). `seed`,
+        `chain_offset` and `x0` as sample_device: shards of a run are bit-identical to the whole run, and the base
+        density N(mean, std^2 I) is evaluated at the f32 start state whichever way it came. With the unnormalised
+        log posterior at x these are importance weights (evaluate.importance_report). CDE and
+        PosteriorDiffusionEstimator; there is no CPU path, and a shape or activation without a compiled kernel
+        raises ValueError."""
+        nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: sample_with_log_prob is implemented for "
+                                                     "CDE and PosteriorDiffusionEstimator only"))
+        single = torch.as_tensor(y).ndim == 1
+        n_y = torch.as_tensor(y).reshape(-1, self.ydim).shape[0]
+        if x0 is not None:
+            shape = tuple(torch.as_tensor(x0).shape)
+            if shape != (n_y, int(num_samples), self.xdim) and not (n_y == 1 and shape == (int(num_samples), self.xdim)):
+                raise ValueError("x0 must have shape (n_y, num_samples, xdim), or (num_samples, xdim) for one y")
+        if int(num_samples) < 1 or int(num_steps) < 1:
+            raise ValueError("sample_with_log_prob: num_samples and num_steps must be >= 1")
+        if not float(std) > 0.0:
+            raise ValueError(f"sample_with_log_prob: std must be > 0, got {std}")
+        layers = [list(n.hidden_layers) for n in nets]
+        widths = set(w for hl in layers for w in hl)
+        if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
+                not _lib.flow_sample_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode):
+            raise ValueError(f"sample_with_log_prob: no compiled kernel for hidden layers {layers}, xdim {self.xdim}")
+        if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
+            raise ValueError("sample_with_log_prob: the kernel computes the tanh chain only")
+        from . import parallel
+        dev, ys, sde, out = self._prepare(y, num_samples, num_steps, nets)
+        x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
+        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
+        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        logq = torch.empty(ys.shape[0], int(num_samples), device=dev, dtype=torch.float32)
+        seed = _draw_seed() if seed is None else seed
+        # guarded: the device status word is read after the launch
+        parallel.guarded(dev, lambda: _lib.flow_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps,
+                                                       mean, std, seed, out, logq, x0))
+        return (out[0], logq[0]) if single else (out, logq)
 
     def _exec_device(self, y):
         if isinstance(y, torch.Tensor) and y.is_cuda:

@@ -154,3 +154,58 @@ def evaluate_linear(model, ys, forward_model, out_dir, plot_ys, n_samples_x=5000
                                  'MSE': mse_vals})
         print('KL2:', kl2_vals.mean(), '+-', np.mean((kl2_vals - kl2_vals.mean()) ** 2))
     return kl2_vals.mean(), nlpd.mean(), float(np.mean(mse_vals))
+
+
+# --------------------------------------------------------------------------- importance sampling with log q
+def _f64(v):
+    v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    return np.asarray(v, np.float64)
+
+
+def importance_report(logq, log_target):
+    """What samples x ~ q with their density say about an unnormalised target: `logq` = log q(x) (e.g. of
+    model.sample_with_log_prob) and `log_target` = the unnormalised log posterior at the same samples, both (n,) or
+    (n_y, n), tensors or arrays. Float64 on the host; every exponential is taken of log weights shifted by their
+    row maximum, so no shift of either argument overflows. Returns a dict, per row of (n_y, n) inputs ((n,) inputs:
+    scalars, weights (n,)):
+        ess         (sum w)^2 / sum w^2 of w = target / q: the effective sample size, in [1, n]
+        ess_frac    ess / n
+        log_z       log mean w: the log evidence of the target under q (log of its normalising constant)
+        reverse_kl  mean(logq - log_target) + log_z: the Monte-Carlo KL(q || target / Z) with the estimated Z
+        weights     w / sum w
+    """
+    lq, lt = _f64(logq), _f64(log_target)
+    if lq.shape != lt.shape or lq.ndim not in (1, 2) or lq.shape[-1] < 1:
+        raise ValueError("importance_report: logq and log_target must both be (n,) or (n_y, n)")
+    lw = lt - lq
+    n = lw.shape[-1]
+    mx = lw.max(axis=-1, keepdims=True)
+    w = np.exp(lw - mx)
+    s1, s2 = w.sum(axis=-1), (w * w).sum(axis=-1)
+    ess = s1 * s1 / s2
+    log_z = np.log(s1 / n) + mx[..., 0]
+    # mean(-lw) + log_z with the shift taken out first: exact 0 for target == q whatever the common offset
+    reverse_kl = np.log(s1 / n) - (lw - mx).mean(axis=-1)
+    out = {"ess": ess, "ess_frac": ess / n, "log_z": log_z, "reverse_kl": reverse_kl, "weights": w / s1[..., None]}
+    return {k: (float(v) if np.ndim(v) == 0 else v) for k, v in out.items()}
+
+
+def importance_posterior(model, y, log_target_fn, num_samples=4096, num_steps=200, seed=None):
+    """Self-checking posterior samples for one observation y (ydim,): model.sample_with_log_prob, then
+    importance_report against `log_target_fn(x)` -> (n,), the unnormalised log posterior at the device samples
+    x (n, xdim). Targets of the two problems of this package:
+        linear          post = LinearForwardProblem().get_posterior(y.cpu(), device='cpu')
+                        lambda x: post.log_prob(x.cpu())      (the drivers' way: the 2 x 2 Gaussian on the host)
+        scatterometry   lambda x: -get_log_posterior(x, forward_model, a, b, y, lambd_bd)
+                        (get_log_posterior returns the negative log posterior, (n, 1) or (n,): it is flattened)
+    Returns importance_report's dict plus x (n, xdim) and logq (n,) (device tensors) and, in float64 numpy,
+    mean (the plain sample mean of x), snis_mean and snis_cov (the self-normalised importance-sampling mean and
+    covariance: sum_i w_i x_i and sum_i w_i (x_i - m)(x_i - m)^T with the normalised weights)."""
+    x, logq = model.sample_with_log_prob(torch.as_tensor(y).reshape(-1), num_samples, num_steps, seed=seed)
+    lt = torch.as_tensor(log_target_fn(x)).reshape(-1)
+    rep = importance_report(logq, lt)
+    xs, w = _f64(x), rep["weights"]
+    m = w @ xs
+    r = xs - m
+    rep.update(x=x, logq=logq, mean=xs.mean(axis=0), snis_mean=m, snis_cov=(w[:, None] * r).T @ r)
+    return rep

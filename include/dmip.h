@@ -216,6 +216,27 @@ int dmip_ode_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const 
                     float* snap_out_dev, float* x_out_dev, void* stream);
 int dmip_ode_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision, int solver);
 
+/* Samples of the probability-flow ODE together with their model log-density, exact f32, one launch: the steps of
+ * dmip_ode_sample's DMIP_SOLVER_HEUN at DMIP_PREC_F32 (same grid, same m, same f32 rounding order, same x0: x_out is
+ * that sampler's x_out) and, beside them, the divergence of the drift from forward tangents through the network
+ * (the columns of dmip_flow_logp):
+ *   dm(x, i) = 1/2 g_i sum_j da_j/dx_j (x, y, tau_i) + 1/2 beta_i d
+ *   J = (delta/2) sum_i (dm(x_i, i) + dm(x~_i, i + 1))                                        (f64 sum, 2 S terms)
+ *   log q(x_S | y) = -(d/2) log 2 pi - d log stdv - 1/2 |(x_0 - mean) / stdv|^2 - J           (f64, stored as f32)
+ * (for DMIP_SAMPLER_POSTERIOR a = g_i (likelihood + prior), so its divergence carries g_i as well).
+ *   x0_dev        [n_y][n_chains][xdim] start states, or null: the chain's own x0 (as dmip_ode_sample); either way
+ *                 the base density is evaluated at the f32 x_0, so passing the seed path's own x0 gives the same bits
+ *   x_out_dev     [n_y][n_chains][xdim];  logq_out_dev [n_y][n_chains]
+ * chain_offset shards a run bit-identically, as for every sampler. Modes other than CDE / Posterior, null arguments
+ * (x0_dev excepted), n_chains < 1, num_steps < 1 and stdv <= 0 are DMIP_ERR_INVALID; a SiLU network and a shape
+ * without a kernel are DMIP_ERR_UNSUPPORTED; every argument is validated before any device work. Shapes:
+ * dmip_flow_sample_supported (those of dmip_flow_logp_supported). */
+int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                     int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                     float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev, float* logq_out_dev,
+                     void* stream);
+int dmip_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim);
+
 /* ---- training: fused loss value + parameter gradients ----------------------------------------- */
 typedef enum { DMIP_LOSS_DSM = 0, DMIP_LOSS_DSM_PDE = 1, DMIP_LOSS_PINN = 2, DMIP_LOSS_PINN2 = 3 } dmip_loss_kind;
 typedef enum { DMIP_PDE_NONE = 0, DMIP_PDE_FPE = 1, DMIP_PDE_CFPE = 2 } dmip_pde_kind;
