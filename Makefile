@@ -7,7 +7,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall 
 F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(CSRC)/dmip_f32_cdiffe.o $(CSRC)/dmip_flow.o \
            $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
-          $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o
+          $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o \
+          $(CSRC)/dmip_x3_flow.o $(CSRC)/dmip_x3_flow_cde.o $(CSRC)/dmip_x3_flow_post.o \
+          $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o
 # the C-ABI layer by concern: packers and handles, sampling entry points, training entry points
 CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train
 CAPIOBJS := $(patsubst %,$(CSRC)/%.o,$(CAPI))
@@ -60,6 +62,14 @@ $(CSRC)/dmip_x3.o: $(CSRC)/dmip_x3.hip $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/dmip_x3_%.o: $(CSRC)/dmip_x3_%.hip $(CSRC)/dmip_x3.h $(CSRC)/dmip_x3s.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# log p(x | y) and samples with their log-density on the fp32x3 engine: free functions beside it (dmip_x3_flow.h),
+# the dispatch and four translation units of instantiations
+$(CSRC)/dmip_x3_flow.o: $(CSRC)/dmip_x3_flow.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_x3.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+$(CSRC)/dmip_x3_flow_%.o: $(CSRC)/dmip_x3_flow_%.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 # the k-major multi-tile fp32x3 CDE engine (width 256): its own header

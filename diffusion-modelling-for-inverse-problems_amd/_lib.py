@@ -42,6 +42,8 @@ EXPORTED = (
     "dmip_train_plan_set_counters", "dmip_train_plan_destroy", "dmip_sampler_supported_precision",
     "dmip_dps_sample_ex", "dmip_mh_sample_ex", "dmip_em_sample_lmbd", "dmip_flow_logp", "dmip_flow_logp_supported",
     "dmip_ode_sample", "dmip_ode_sample_supported", "dmip_flow_sample", "dmip_flow_sample_supported",
+    "dmip_flow_logp_ex", "dmip_flow_sample_ex", "dmip_flow_logp_supported_precision",
+    "dmip_flow_sample_supported_precision",
 )
 DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
 SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
@@ -141,6 +143,14 @@ def _declare(lib):
                                          _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _c_void_p, _c_void_p, _c_void_p,
                                          _c_void_p]
         lib.dmip_flow_sample_supported.argtypes = [_i32, _i32, _i32, _i32, _i32]
+    if hasattr(lib, "dmip_flow_logp_ex"):  # (absent from older builds loaded by A/B timing scripts)
+        lib.dmip_flow_logp_ex.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p,
+                                          _i32, _i32, _i32, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p]
+        lib.dmip_flow_sample_ex.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32,
+                                            _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _c_void_p, _c_void_p,
+                                            _c_void_p, _i32, _c_void_p]
+        lib.dmip_flow_logp_supported_precision.argtypes = [_i32] * 6
+        lib.dmip_flow_sample_supported_precision.argtypes = [_i32] * 6
     if hasattr(lib, "dmip_train_plan_create"):
         lib.dmip_train_plan_create.argtypes = [ctypes.POINTER(DmipTrainPlanDesc), ctypes.POINTER(_c_void_p)]
         lib.dmip_train_plan_step.argtypes = [_c_void_p, _c_void_p, _c_void_p, _c_void_p]
@@ -394,32 +404,54 @@ def ode_sample(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean
                                 ptr(snaps), ptr(out), stream_of(y.device)))
 
 
-def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE):
-    return bool(lib().dmip_flow_logp_supported(mode, width, n_hidden, xdim, ydim))
+def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32"):
+    """Whether dmip_flow_logp[_ex] has a kernel: "fp32" the exact-f32 engine, "fp32x3" (and "fp16" / "bf16", which
+    run it) the split engine."""
+    if precision == "fp32":
+        return bool(lib().dmip_flow_logp_supported(mode, width, n_hidden, xdim, ydim))
+    return bool(lib().dmip_flow_logp_supported_precision(precision_code(precision), mode, width, n_hidden, xdim, ydim))
 
 
-def flow_logp(mode, net, prior, sde, x, y, num_steps, logp, latent=None):
-    """dmip_flow_logp: log p(x | y) of x (n_y, n, xdim) under ys (n_y, ydim) into logp (n_y, n) [and x_S into latent]."""
+def flow_logp(mode, net, prior, sde, x, y, num_steps, logp, latent=None, precision="fp32"):
+    """dmip_flow_logp: log p(x | y) of x (n_y, n, xdim) under ys (n_y, ydim) into logp (n_y, n) [and x_S into latent].
+    precision "fp32" is that entry point; any other goes through dmip_flow_logp_ex (the fp32x3 kernels)."""
+    code = precision_code(precision)
     calls["flow_logp"] += 1
     _status_pending.add(_dev_index(y.device))  # (parallel.guarded then reads the status word after the launch)
     n_y, ydim = y.shape
-    check(lib().dmip_flow_logp(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(x), ptr(y), n_y, ydim, net.xdim,
-                               int(x.shape[1]), int(num_steps), ptr(logp), ptr(latent), stream_of(y.device)))
+    if code == DMIP_PREC_F32:
+        check(lib().dmip_flow_logp(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(x), ptr(y), n_y, ydim, net.xdim,
+                                   int(x.shape[1]), int(num_steps), ptr(logp), ptr(latent), stream_of(y.device)))
+        return
+    check(lib().dmip_flow_logp_ex(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(x), ptr(y), n_y, ydim, net.xdim,
+                                  int(x.shape[1]), int(num_steps), ptr(logp), ptr(latent), code, stream_of(y.device)))
 
 
-def flow_sample_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE):
-    return bool(lib().dmip_flow_sample_supported(mode, width, n_hidden, xdim, ydim))
+def flow_sample_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32"):
+    """flow_logp_supported's answer for dmip_flow_sample[_ex]."""
+    if precision == "fp32":
+        return bool(lib().dmip_flow_sample_supported(mode, width, n_hidden, xdim, ydim))
+    return bool(lib().dmip_flow_sample_supported_precision(precision_code(precision), mode, width, n_hidden, xdim,
+                                                           ydim))
 
 
-def flow_sample(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, out, logq, x0=None):
+def flow_sample(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, out, logq, x0=None,
+                precision="fp32"):
     """dmip_flow_sample: Heun samples of the probability-flow ODE into out (n_y, n_chains, xdim) with their
-    log-density into logq (n_y, n_chains), exact f32; x0 (n_y, n_chains, xdim) replaces the chains' own start states."""
+    log-density into logq (n_y, n_chains); x0 (n_y, n_chains, xdim) replaces the chains' own start states. precision
+    "fp32" is that entry point (exact f32); any other goes through dmip_flow_sample_ex (the fp32x3 kernels)."""
+    code = precision_code(precision)
     calls["flow_sample"] += 1
     _status_pending.add(_dev_index(y.device))  # (parallel.guarded then reads the status word after the launch)
     n_y, ydim = y.shape
-    check(lib().dmip_flow_sample(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
-                                 int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std), _u64(seed),
-                                 ptr(x0), ptr(out), ptr(logq), stream_of(y.device)))
+    if code == DMIP_PREC_F32:
+        check(lib().dmip_flow_sample(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
+                                     int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std),
+                                     _u64(seed), ptr(x0), ptr(out), ptr(logq), stream_of(y.device)))
+        return
+    check(lib().dmip_flow_sample_ex(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
+                                    int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std),
+                                    _u64(seed), ptr(x0), ptr(out), ptr(logq), code, stream_of(y.device)))
 
 
 def sampler_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp16"):

@@ -476,57 +476,102 @@ int dmip_em_sample_stamps(const dmip_mlp* net, const dmip_vpsde* sde, const floa
   return em_sample_impl(DMIP_SAMPLER_CDE, net, nullptr, a);
 }
 
-int dmip_flow_logp_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
-  return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+}  // extern "C"
+
+namespace {
+
+// the flow entry points' precision: exact f32 (dmip_flow.hip, dmip_flow_sample.hip), or the fp32x3 engine
+// (dmip_x3_flow.h) -- which DMIP_PREC_FP16 / BF16 run as well: there is no 16-bit flow kernel (as dmip_ode_sample's
+// Heun routing has none)
+int check_flow_precision(int precision) {
+  if (precision != DMIP_PREC_FP16 && precision != DMIP_PREC_F32 && precision != DMIP_PREC_F32X3)
+    return fail(DMIP_ERR_INVALID, "unknown precision");
+  return DMIP_OK;
 }
 
-// log p(x | y) along the probability-flow ODE (dmip_flow.hip); every argument is validated before any device work
-int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
+// what em_sample_x3 checks before an fp32x3 launch: the networks have their split images
+int x3_flow_check(const char* kind, int mode, const dmip_mlp* net, const dmip_mlp* net1, int xdim) {
+  for (const dmip_mlp* n : {net, net1})
+    if (n && n->x3_range > 0.0)
+      return fail(DMIP_ERR_UNSUPPORTED, "fp32x3: a weight is outside the fp16 range of the split engine (largest "
+                                        "scaled |w| " + std::to_string(n->x3_range) + " > 65504); use DMIP_PREC_F32");
+  if (!net->x3_stream || (net1 && !net1->x3_stream)) return no_kernel(kind, mode, net, xdim, -1, DMIP_PREC_F32X3);
+  return DMIP_OK;
+}
+
+// and what it prepares: the images' pointers and the per-y layer-1 bias c (b1 + W1_y y) (f64 prep)
+int x3_flow_prep(const dmip_mlp* net, const dmip_mlp* net1, const float* y_dev, int n_y, int xdim, int ydim,
+                 hipStream_t st, StreamScratch& bias_y, dmip::X3Net (&nets)[2]) {
+  nets[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
+  if (net1) nets[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
+  if (int rc = bias_y.alloc((size_t)n_y * net->width * sizeof(float), st)) return rc;
+  dmip::X3BiasPrepParams bp{net->w1, net->b1, y_dev, (float*)bias_y.ptr, net->width, net->in_dim, xdim, ydim};
+  const hipError_t e = dmip::launch_x3_bias_prep(bp, n_y, st);
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "x3 bias prep launch");
+}
+
+// log p(x | y) along the probability-flow ODE; every argument is validated before any device work
+int flow_logp_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
                    const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
-                   float* latent_out_dev, void* stream) {
+                   float* latent_out_dev, int precision, void* stream) {
   if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
     return fail(DMIP_ERR_INVALID, "flow_logp: CDE and Posterior estimators only");
   if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
   if (!net || !sde || !x_dev || !y_dev || !logp_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
     return fail(DMIP_ERR_INVALID, "null argument");
+  if (int rc = check_flow_precision(precision)) return rc;
   const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
   if (int rc = check_nets("flow_logp", net, net1, xdim, xdim, ydim, n_y, true, n, 0, num_steps, sde)) return rc;
   if (f32_act(net) || (net1 && f32_act(net1)))
     return fail(DMIP_ERR_UNSUPPORTED, "flow_logp: the tanh chain only (no SiLU log-likelihood kernel)");
-  if (!dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim))
-    return no_kernel("log-likelihood kernel", mode, net, xdim);
-  if (n == 0) return DMIP_OK;
+  const bool x3 = precision != DMIP_PREC_F32;
+  if (!(x3 ? dmip::x3_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)
+           : dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)))
+    return no_kernel("log-likelihood kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
   hipStream_t st = (hipStream_t)stream;
-  dmip::F32FlowParams p{};
-  p.net[0] = f32_net(net);
-  if (net1) p.net[1] = f32_net(net1);
-  p.n_hidden = net->n_hidden;
-  StreamScratch l1y;
-  if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
-  p.l1y = (float*)l1y.ptr;
-  p.x = x_dev;
-  p.logp = logp_out_dev;
-  p.latent = latent_out_dev;
-  p.n = n;
-  p.num_steps = num_steps;
-  fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.h);
+  auto fill_rows = [&](auto& p) {  // what F32FlowParams and X3FlowParams share
+    p.n_hidden = net->n_hidden;
+    p.x = x_dev;
+    p.logp = logp_out_dev;
+    p.latent = latent_out_dev;
+    p.n = n;
+    p.num_steps = num_steps;
+    fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.h);
+  };
   bool ok = false;
-  const hipError_t e = dmip::launch_f32_flow(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  hipError_t e;
+  if (x3) {
+    dmip::X3FlowParams p{};
+    StreamScratch bias_y;
+    if (int rc = x3_flow_check("log-likelihood kernel", mode, net, net1, xdim)) return rc;
+    if (n == 0) return DMIP_OK;
+    if (int rc = x3_flow_prep(net, net1, y_dev, n_y, xdim, ydim, st, bias_y, p.net)) return rc;
+    p.bias_y = (float*)bias_y.ptr;
+    fill_rows(p);
+    p.err = status_word(dmip::stream_device(st));
+    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+    e = dmip::launch_x3_flow(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  } else {
+    if (n == 0) return DMIP_OK;
+    dmip::F32FlowParams p{};
+    p.net[0] = f32_net(net);
+    if (net1) p.net[1] = f32_net(net1);
+    StreamScratch l1y;
+    if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
+    p.l1y = (float*)l1y.ptr;
+    fill_rows(p);
+    e = dmip::launch_f32_flow(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  }
   if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled log-likelihood kernel");
   if (e != hipSuccess) return hip_fail(e, "flow_logp launch");
   return DMIP_OK;
 }
 
-int dmip_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
-  return dmip::f32_flow_sample_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
-}
-
-// samples of the probability-flow ODE with their log-density (dmip_flow_sample.hip); every argument is validated
-// before any device work
-int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+// samples of the probability-flow ODE with their log-density; every argument is validated before any device work
+int flow_sample_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
                      int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
                      float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev, float* logq_out_dev,
-                     void* stream) {
+                     int precision, void* stream) {
   if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
     return fail(DMIP_ERR_INVALID, "flow_sample: CDE and Posterior estimators only");
   if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
@@ -534,38 +579,115 @@ int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const
   if (!(stdv > 0.0f)) return fail(DMIP_ERR_INVALID, "stdv must be > 0");
   if (!net || !sde || !y_dev || !x_out_dev || !logq_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
     return fail(DMIP_ERR_INVALID, "null argument");
+  if (int rc = check_flow_precision(precision)) return rc;
   const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
   if (int rc = check_nets("flow_sample", net, net1, xdim, xdim, ydim, n_y, false, n_chains, chain_offset, num_steps,
                           sde))
     return rc;
   if (f32_act(net) || (net1 && f32_act(net1)))
     return fail(DMIP_ERR_UNSUPPORTED, "flow_sample: the tanh chain only (no SiLU kernel)");
-  if (!dmip::f32_flow_sample_supported(mode, net->width, net->n_hidden, xdim, ydim))
-    return no_kernel("flow_sample kernel", mode, net, xdim);
+  const bool x3 = precision != DMIP_PREC_F32;
+  if (!(x3 ? dmip::x3_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)
+           : dmip::f32_flow_sample_supported(mode, net->width, net->n_hidden, xdim, ydim)))
+    return no_kernel("flow_sample kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
   hipStream_t st = (hipStream_t)stream;
-  dmip::F32FlowSampleParams p{};
-  p.net[0] = f32_net(net);
-  if (net1) p.net[1] = f32_net(net1);
-  p.n_hidden = net->n_hidden;
-  StreamScratch l1y;
-  if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
-  p.l1y = (float*)l1y.ptr;
-  p.x0 = x0_dev;
-  p.x_out = x_out_dev;
-  p.logq = logq_out_dev;
-  p.n = n_chains;
-  p.chain_offset = chain_offset;
-  p.num_steps = num_steps;
-  fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.delta);
-  p.mean = mean;
-  p.stdv = stdv;
-  p.seed = seed;
-  p.base = -0.5 * (double)xdim * 1.8378770664093453 - (double)xdim * std::log((double)stdv);  // log 2 pi
+  auto fill_chains = [&](auto& p) {  // what F32FlowSampleParams and X3FlowSampleParams share
+    p.n_hidden = net->n_hidden;
+    p.x0 = x0_dev;
+    p.x_out = x_out_dev;
+    p.logq = logq_out_dev;
+    p.n = n_chains;
+    p.chain_offset = chain_offset;
+    p.num_steps = num_steps;
+    fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.delta);
+    p.mean = mean;
+    p.stdv = stdv;
+    p.seed = seed;
+    p.base = -0.5 * (double)xdim * 1.8378770664093453 - (double)xdim * std::log((double)stdv);  // log 2 pi
+  };
   bool ok = false;
-  const hipError_t e = dmip::launch_f32_flow_sample(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  hipError_t e;
+  if (x3) {
+    dmip::X3FlowSampleParams p{};
+    StreamScratch bias_y;
+    if (int rc = x3_flow_check("flow_sample kernel", mode, net, net1, xdim)) return rc;
+    if (int rc = x3_flow_prep(net, net1, y_dev, n_y, xdim, ydim, st, bias_y, p.net)) return rc;
+    p.bias_y = (float*)bias_y.ptr;
+    fill_chains(p);
+    p.err = status_word(dmip::stream_device(st));
+    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+    e = dmip::launch_x3_flow_sample(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  } else {
+    dmip::F32FlowSampleParams p{};
+    p.net[0] = f32_net(net);
+    if (net1) p.net[1] = f32_net(net1);
+    StreamScratch l1y;
+    if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
+    p.l1y = (float*)l1y.ptr;
+    fill_chains(p);
+    e = dmip::launch_f32_flow_sample(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
+  }
   if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled flow_sample kernel");
   if (e != hipSuccess) return hip_fail(e, "flow_sample launch");
   return DMIP_OK;
+}
+
+// the tanh chain's answer, as dmip_sampler_supported_precision's
+int flow_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
+  if (precision == DMIP_PREC_F32) return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+  if (precision == DMIP_PREC_F32X3 || precision == DMIP_PREC_FP16)
+    return dmip::x3_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmip_flow_logp_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
+  return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+}
+
+int dmip_flow_logp_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
+  return flow_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
+}
+
+int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
+                   const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
+                   float* latent_out_dev, void* stream) {
+  return flow_logp_impl(mode, net, prior, sde, x_dev, y_dev, n_y, ydim, xdim, n, num_steps, logp_out_dev,
+                        latent_out_dev, DMIP_PREC_F32, stream);
+}
+
+int dmip_flow_logp_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
+                      const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
+                      float* latent_out_dev, int precision, void* stream) {
+  return flow_logp_impl(mode, net, prior, sde, x_dev, y_dev, n_y, ydim, xdim, n, num_steps, logp_out_dev,
+                        latent_out_dev, precision, stream);
+}
+
+int dmip_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
+  return dmip::f32_flow_sample_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
+}
+
+int dmip_flow_sample_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
+  return flow_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
+}
+
+int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
+                     int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
+                     float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev, float* logq_out_dev,
+                     void* stream) {
+  return flow_sample_impl(mode, net, prior, sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv,
+                          seed, x0_dev, x_out_dev, logq_out_dev, DMIP_PREC_F32, stream);
+}
+
+int dmip_flow_sample_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                        const float* y_dev, int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset,
+                        int num_steps, float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
+                        float* logq_out_dev, int precision, void* stream) {
+  return flow_sample_impl(mode, net, prior, sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv,
+                          seed, x0_dev, x_out_dev, logq_out_dev, precision, stream);
 }
 
 }  // extern "C"

@@ -415,6 +415,40 @@ hipError_t launch_x3k_sampler(const X3SamplerParams& p, int xdim, int n_y, hipSt
 bool x3p_sampler_supported(int mode, int width, int n_hidden, int xdim);
 hipError_t launch_x3p_sampler(const X3SamplerParams& p, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_x3_bias_prep(const X3BiasPrepParams& p, int n_y, hipStream_t st);
+// the probability-flow kernels on the fp32x3 engine (dmip_x3_flow.h): F32FlowParams / F32FlowSampleParams with the
+// split engine's images, the per-y layer-1 bias of the samplers and the device status word (kErrRange)
+struct X3FlowParams {
+  X3Net net[2];               // net 0: CDE / likelihood; net 1: the Posterior prior
+  const float* bias_y;        // per-y layer-1 bias c (b1 + W1_y y) [n_y][W]
+  int n_hidden;
+  const float* x;             // [n_y][n][D]
+  float* logp;                // [n_y][n]
+  float* latent;              // [n_y][n][D] x_S, or null
+  long long n;                // rows per y
+  int num_steps;
+  float T, bmin, bdiff, h;    // h = T / num_steps
+  unsigned int* err;
+};
+struct X3FlowSampleParams {
+  X3Net net[2];
+  const float* bias_y;
+  int n_hidden;
+  const float* x0;            // start states [n_y][n][D] or null (randn stdv + mean from the RNG)
+  float* x_out;               // [n_y][n][D]
+  float* logq;                // [n_y][n]
+  long long n, chain_offset;  // chains per y; the RNG's chain index of row 0
+  int num_steps;
+  float T, bmin, bdiff, delta, mean, stdv;
+  unsigned long long seed;
+  double base;                // -(D/2) log 2 pi - D log stdv
+  unsigned int* err;
+};
+// CDE and Posterior, xdim 2 or 3, any ydim, 1 to 3 hidden layers, widths 64 / 128 / 256 / 512 (dmip_x3_flow.hip)
+bool x3_flow_supported(int mode, int width, int n_hidden, int xdim, int ydim);
+hipError_t launch_x3_flow(const X3FlowParams& p, int mode, int width, int n_hidden, int xdim, int ydim, int n_y,
+                          hipStream_t st, bool* supported);
+hipError_t launch_x3_flow_sample(const X3FlowSampleParams& p, int mode, int width, int n_hidden, int xdim, int ydim,
+                                 int n_y, hipStream_t st, bool* supported);
 // geometry of the x3 images (dmip_x3.h Shape) for the host packer
 int x3_chunk_bytes(int width);
 int x3_tiles_per_chunk(int width);

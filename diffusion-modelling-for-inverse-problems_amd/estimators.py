@@ -11,7 +11,8 @@ CDE and PosteriorDiffusionEstimator sample the whole lambda family of the refere
 (sdes.py:77-87) with `lmbd=`: 0 the reverse SDE (the default), 1 the deterministic probability-flow ODE
 (dmip_em_sample_lmbd), and `model.log_prob(x, y)` is the model's own log-density log p(x | y) along that ODE
 (dmip_flow_logp, exact f32); `model.sample_with_log_prob(y, n)` draws samples of that ODE together with their
-log-density in one launch (dmip_flow_sample, exact f32).
+log-density in one launch (dmip_flow_sample, exact f32). Both take `precision="fp32x3"` for the same scheme on the
+split-fp16 engine (dmip_flow_logp_ex / dmip_flow_sample_ex); their default is exact f32 whatever `model.precision` is.
 Precision (`model.precision`, or `precision=` per call; default from $DMIP_PRECISION, else "fp32x3"):
   "fp32x3" -- the reference's fp32 arithmetic at the fp16 matrix rate: every product as three fp16 MFMAs
              (W_hi h_hi + W_hi h_lo + W_lo h_hi, fp32 accumulation; csrc/dmip_x3.h), tanh by exp2 + rcp.
@@ -144,6 +145,17 @@ def _nets_and_mode(model, error, cdiffe=False):
     raise error
 
 
+def _flow_precision(precision):
+    """The precision of log_prob / sample_with_log_prob: None is "fp32" (what they ran before they took one)."""
+    precision = "fp32" if precision is None else precision
+    _lib.precision_code(precision)  # ValueError for an unknown name, before anything else
+    return precision
+
+
+def _flow_hint(precision):
+    return "" if precision == "fp32" else f' at precision="{precision}" (precision="fp32" has the exact-f32 kernels)'
+
+
 def _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec,
                   lmbd=0.0, solver="euler", x0=None, noise=None):
     """The fused CDE / Posterior launch of sample_device: dmip_ode_sample for Heun, dmip_em_sample_lmbd for
@@ -234,21 +246,25 @@ class BaseClassDiffusionModel:
                                  snapshot_every, snaps, out, corrector_steps, snr, prec)
         return out, snaps
 
-    def log_prob(self, x, y, num_steps=200, return_latent=False):
+    def log_prob(self, x, y, num_steps=200, return_latent=False, precision=None):
         """The model's own log-density log p(x | y) by the instantaneous change of variables along the
         probability-flow ODE (lmbd = 1; Song et al. 2021, section 4.3): num_steps Heun steps from x to the latent
         x_S ~ N(0, I), the divergence of the score network exact (forward tangents), in exact f32 in one launch
         (dmip_flow_logp). x (n, xdim) with one y (ydim,) -> a float32 device tensor (n,); x (n_y, n, xdim) with ys
         (n_y, ydim) -> (n_y, n). return_latent=True: (logp, x_S), x_S shaped as x. CDE and
         PosteriorDiffusionEstimator; like sampling there is no CPU path, and a shape or activation without a
-        compiled kernel raises ValueError."""
+        compiled kernel raises ValueError. precision: None is "fp32" (exact f32); "fp32x3" runs the same scheme on
+        the split-fp16 engine (dmip_flow_logp_ex; "fp16" / "bf16" run it too: there is no 16-bit kernel) -- a row
+        beyond the split's range then raises "fp16 range", as an explicit precision="fp32x3" sampler call does."""
         nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: log_prob is implemented for CDE and "
                                                      "PosteriorDiffusionEstimator only"))
+        precision = _flow_precision(precision)
         layers = [list(n.hidden_layers) for n in nets]
         widths = set(w for hl in layers for w in hl)
         if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
-                not _lib.flow_logp_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode):
-            raise ValueError(f"log_prob: no compiled log-likelihood kernel for hidden layers {layers}, xdim {self.xdim}")
+                not _lib.flow_logp_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
+            raise ValueError(f"log_prob: no compiled log-likelihood kernel for hidden layers {layers}, xdim {self.xdim}"
+                             + _flow_hint(precision))
         if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
             raise ValueError("log_prob: the log-likelihood kernel computes the tanh chain only")
         from . import parallel
@@ -265,12 +281,14 @@ class BaseClassDiffusionModel:
         logp = torch.empty(xs.shape[0], xs.shape[1], device=dev, dtype=torch.float32)
         latent = torch.empty_like(xs) if return_latent else None
         # guarded: the device status word is read after the launch
-        parallel.guarded(dev, lambda: _lib.flow_logp(mode, net, prior, sde, xs, ys, num_steps, logp, latent))
+        parallel.guarded(dev, lambda: _lib.flow_logp(mode, net, prior, sde, xs, ys, num_steps, logp, latent,
+                                                     precision))
         if single:
             logp, latent = logp[0], (latent[0] if return_latent else None)
         return (logp, latent) if return_latent else logp
 
-    def sample_with_log_prob(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, x0=None):
+    def sample_with_log_prob(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, x0=None,
+                             precision=None):
         """Samples x ~ q(. | y) of the probability-flow ODE together with their model log-density log q(x | y), in
         exact f32 in one launch (dmip_flow_sample): the steps of sample_device(solver="heun", precision="fp32") --
         the same x at the same seed -- with the divergence of the drift (exact, forward tangents) integrated beside
@@ -281,9 +299,12 @@ class BaseClassDiffusionModel:
         density N(mean, std^2 I) is evaluated at the f32 start state whichever way it came. With the unnormalised
         log posterior at x these are importance weights (evaluate.importance_report). CDE and
         PosteriorDiffusionEstimator; there is no CPU path, and a shape or activation without a compiled kernel
-        raises ValueError."""
+        raises ValueError. precision: None is "fp32"; "fp32x3" (and "fp16" / "bf16", which run it) is the split-fp16
+        engine (dmip_flow_sample_ex): the x of sample_device(solver="heun", precision="fp32x3") at the same seed, and
+        "fp16 range" raised for a chain beyond the split's range."""
         nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: sample_with_log_prob is implemented for "
                                                      "CDE and PosteriorDiffusionEstimator only"))
+        precision = _flow_precision(precision)
         single = torch.as_tensor(y).ndim == 1
         n_y = torch.as_tensor(y).reshape(-1, self.ydim).shape[0]
         if x0 is not None:
@@ -297,8 +318,9 @@ class BaseClassDiffusionModel:
         layers = [list(n.hidden_layers) for n in nets]
         widths = set(w for hl in layers for w in hl)
         if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
-                not _lib.flow_sample_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode):
-            raise ValueError(f"sample_with_log_prob: no compiled kernel for hidden layers {layers}, xdim {self.xdim}")
+                not _lib.flow_sample_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
+            raise ValueError(f"sample_with_log_prob: no compiled kernel for hidden layers {layers}, xdim {self.xdim}"
+                             + _flow_hint(precision))
         if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
             raise ValueError("sample_with_log_prob: the kernel computes the tanh chain only")
         from . import parallel
@@ -310,7 +332,7 @@ class BaseClassDiffusionModel:
         seed = _draw_seed() if seed is None else seed
         # guarded: the device status word is read after the launch
         parallel.guarded(dev, lambda: _lib.flow_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps,
-                                                       mean, std, seed, out, logq, x0))
+                                                       mean, std, seed, out, logq, x0, precision))
         return (out[0], logq[0]) if single else (out, logq)
 
     def _exec_device(self, y):

@@ -190,7 +190,7 @@ def importance_report(logq, log_target):
     return {k: (float(v) if np.ndim(v) == 0 else v) for k, v in out.items()}
 
 
-def importance_posterior(model, y, log_target_fn, num_samples=4096, num_steps=200, seed=None):
+def importance_posterior(model, y, log_target_fn, num_samples=4096, num_steps=200, seed=None, precision=None):
     """Self-checking posterior samples for one observation y (ydim,): model.sample_with_log_prob, then
     importance_report against `log_target_fn(x)` -> (n,), the unnormalised log posterior at the device samples
     x (n, xdim). Targets of the two problems of this package:
@@ -200,8 +200,10 @@ def importance_posterior(model, y, log_target_fn, num_samples=4096, num_steps=20
                         (get_log_posterior returns the negative log posterior, (n, 1) or (n,): it is flattened)
     Returns importance_report's dict plus x (n, xdim) and logq (n,) (device tensors) and, in float64 numpy,
     mean (the plain sample mean of x), snis_mean and snis_cov (the self-normalised importance-sampling mean and
-    covariance: sum_i w_i x_i and sum_i w_i (x_i - m)(x_i - m)^T with the normalised weights)."""
-    x, logq = model.sample_with_log_prob(torch.as_tensor(y).reshape(-1), num_samples, num_steps, seed=seed)
+    covariance: sum_i w_i x_i and sum_i w_i (x_i - m)(x_i - m)^T with the normalised weights). `precision` is
+    sample_with_log_prob's (None: exact f32; "fp32x3": the split-fp16 engine)."""
+    x, logq = model.sample_with_log_prob(torch.as_tensor(y).reshape(-1), num_samples, num_steps, seed=seed,
+                                         precision=precision)
     lt = torch.as_tensor(log_target_fn(x)).reshape(-1)
     rep = importance_report(logq, lt)
     xs, w = _f64(x), rep["weights"]

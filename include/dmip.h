@@ -237,6 +237,27 @@ int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const
                      void* stream);
 int dmip_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 
+/* dmip_flow_logp and dmip_flow_sample with a precision (ABI 9). DMIP_PREC_F32 is the entry point above, bit for bit.
+ * DMIP_PREC_F32X3 runs the same scheme, columns and f64 sums with the networks and their tangents on the fp32x3 engine
+ * (every product the three-term fp16 split; a tangent column carries dr through the r-form images): at the same seed
+ * dmip_flow_sample_ex's x_out is that of dmip_ode_sample at DMIP_SOLVER_HEUN / DMIP_PREC_F32X3, bit for bit.
+ * DMIP_PREC_FP16 (BF16) runs the fp32x3 kernels too: there is no 16-bit flow kernel, as there is no 16-bit Heun kernel.
+ * A layer-1 input beyond the split's range (|x| > 65504), or a row whose accumulated divergence is not finite, sets
+ * the device status word (dmip_device_status: "fp16 range"); the row's values are still written. A network with a
+ * weight beyond that range is DMIP_ERR_UNSUPPORTED, as for the samplers. Every other argument as above, validated in
+ * the same order with the same codes before any device work; an unknown precision is DMIP_ERR_INVALID. Shapes: the
+ * *_supported_precision queries (DMIP_PREC_F32: the queries above; DMIP_PREC_F32X3 / FP16: CDE and Posterior, widths
+ * 64 / 128 / 256 / 512, 1 to 3 hidden layers, xdim 2 or 3, any ydim; the answer is for the tanh chain). */
+int dmip_flow_logp_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
+                      const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
+                      float* latent_out_dev, int precision, void* stream);
+int dmip_flow_sample_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                        const float* y_dev, int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset,
+                        int num_steps, float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
+                        float* logq_out_dev, int precision, void* stream);
+int dmip_flow_logp_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim);
+int dmip_flow_sample_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim);
+
 /* ---- training: fused loss value + parameter gradients ----------------------------------------- */
 typedef enum { DMIP_LOSS_DSM = 0, DMIP_LOSS_DSM_PDE = 1, DMIP_LOSS_PINN = 2, DMIP_LOSS_PINN2 = 3 } dmip_loss_kind;
 typedef enum { DMIP_PDE_NONE = 0, DMIP_PDE_FPE = 1, DMIP_PDE_CFPE = 2 } dmip_pde_kind;
