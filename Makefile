@@ -49,11 +49,11 @@ $(CSRC)/dmip_f32_%.o: $(CSRC)/dmip_f32_%.hip $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # log p(x | y) along the probability-flow ODE, on the exact-f32 engine's header
-$(CSRC)/dmip_flow.o: $(CSRC)/dmip_flow.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_f32.h $(HDRS)
+$(CSRC)/dmip_flow.o: $(CSRC)/dmip_flow.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # samples with their log-density: the Heun sampler's steps with the log-likelihood kernel's tangent columns
-$(CSRC)/dmip_flow_sample.o: $(CSRC)/dmip_flow_sample.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_f32.h $(HDRS)
+$(CSRC)/dmip_flow_sample.o: $(CSRC)/dmip_flow_sample.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # fp32-accurate split-fp16 engine (DMIP_PREC_F32X3): one header, four translation units; no SLP
@@ -66,10 +66,10 @@ $(CSRC)/dmip_x3_%.o: $(CSRC)/dmip_x3_%.hip $(CSRC)/dmip_x3.h $(CSRC)/dmip_x3s.h 
 
 # log p(x | y) and samples with their log-density on the fp32x3 engine: free functions beside it (dmip_x3_flow.h),
 # the dispatch and four translation units of instantiations
-$(CSRC)/dmip_x3_flow.o: $(CSRC)/dmip_x3_flow.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_x3.h $(HDRS)
+$(CSRC)/dmip_x3_flow.o: $(CSRC)/dmip_x3_flow.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-$(CSRC)/dmip_x3_flow_%.o: $(CSRC)/dmip_x3_flow_%.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_x3.h $(HDRS)
+$(CSRC)/dmip_x3_flow_%.o: $(CSRC)/dmip_x3_flow_%.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 # the k-major multi-tile fp32x3 CDE engine (width 256): its own header

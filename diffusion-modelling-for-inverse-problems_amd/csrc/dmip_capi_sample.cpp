@@ -168,14 +168,32 @@ bool x3p_enabled() {
 }
 #endif
 
+// the refusal of every fp32x3 entry point whose split images could not be packed (`what`: "|w|" or "scaled |w|")
+int x3_range_refused(const char* who, const char* what, double range) {
+  return fail(DMIP_ERR_UNSUPPORTED, std::string(who) + ": a weight is outside the fp16 range of the split engine " +
+                                        "(largest " + what + " " + std::to_string(range) + " > 65504); use DMIP_PREC_F32");
+}
+int x3_check_range(const dmip_mlp* net0, const dmip_mlp* net1) {  // the samplers' and the flow's networks
+  for (const dmip_mlp* n : {net0, net1})
+    if (n && n->x3_range > 0.0) return x3_range_refused("fp32x3", "scaled |w|", n->x3_range);
+  return DMIP_OK;
+}
+
+// the fp32x3 engine's per-y layer-1 bias (the samplers and the flow): y is constant per y index, so c (b1 + W1_y y)
+// becomes layer 1's bias (f64 prep)
+int x3_bias_prep(StreamScratch& bias_y, const dmip_mlp* net, const float* y_dev, int n_y, int xdim, int ydim,
+                 hipStream_t st) {
+  if (int rc = bias_y.alloc((size_t)n_y * net->width * sizeof(float), st)) return rc;
+  dmip::X3BiasPrepParams bp{net->w1, net->b1, y_dev, (float*)bias_y.ptr, net->width, net->in_dim, xdim, ydim};
+  const hipError_t e = dmip::launch_x3_bias_prep(bp, n_y, st);
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "x3 bias prep launch");
+}
+
 // fp32-accurate split-fp16 samplers (dmip_x3.h): same loop, RNG and sharding as the other engines;
 // arguments already validated by em_sample_impl
 int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const SampleArgs& a) {
   const int xdim = a.xdim, ydim = a.ydim;
-  for (const dmip_mlp* n : {net0, net1})
-    if (n && n->x3_range > 0.0)
-      return fail(DMIP_ERR_UNSUPPORTED, "fp32x3: a weight is outside the fp16 range of the split engine (largest "
-                                        "scaled |w| " + std::to_string(n->x3_range) + " > 65504); use DMIP_PREC_F32");
+  if (int rc = x3_check_range(net0, net1)) return rc;
   if (!dmip::x3_sampler_supported(mode, net0->width, net0->n_hidden, xdim, ydim) || !net0->x3_stream ||
       (mode == DMIP_SAMPLER_CDIFFE && !net0->x3_l1_full) || (net1 && !net1->x3_stream))
     return no_kernel("f32x3 sampler", mode, net0, xdim, ydim);
@@ -194,11 +212,7 @@ int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sam
     p.l1_in = net0->in_dim;
     p.ydim = ydim;
   } else if (mode != DMIP_SAMPLER_CDIFFE) {
-    // y is constant per y index: c (b1 + W1_y y) becomes layer 1's per-y bias (f64 prep)
-    if (int rc = bias_y.alloc((size_t)a.n_y * net0->width * sizeof(float), st)) return rc;
-    dmip::X3BiasPrepParams bp{net0->w1, net0->b1, a.y_dev, (float*)bias_y.ptr, net0->width, net0->in_dim, xdim, ydim};
-    const hipError_t e = dmip::launch_x3_bias_prep(bp, a.n_y, st);
-    if (e != hipSuccess) return hip_fail(e, "x3 bias prep launch");
+    if (int rc = x3_bias_prep(bias_y, net0, a.y_dev, a.n_y, xdim, ydim, st)) return rc;
   }
   p.bias_y = (float*)bias_y.ptr;
   if (int rc = fill_common(p, a, st)) return rc;
@@ -491,23 +505,54 @@ int check_flow_precision(int precision) {
 
 // what em_sample_x3 checks before an fp32x3 launch: the networks have their split images
 int x3_flow_check(const char* kind, int mode, const dmip_mlp* net, const dmip_mlp* net1, int xdim) {
-  for (const dmip_mlp* n : {net, net1})
-    if (n && n->x3_range > 0.0)
-      return fail(DMIP_ERR_UNSUPPORTED, "fp32x3: a weight is outside the fp16 range of the split engine (largest "
-                                        "scaled |w| " + std::to_string(n->x3_range) + " > 65504); use DMIP_PREC_F32");
+  if (int rc = x3_check_range(net, net1)) return rc;
   if (!net->x3_stream || (net1 && !net1->x3_stream)) return no_kernel(kind, mode, net, xdim, -1, DMIP_PREC_F32X3);
   return DMIP_OK;
 }
 
-// and what it prepares: the images' pointers and the per-y layer-1 bias c (b1 + W1_y y) (f64 prep)
-int x3_flow_prep(const dmip_mlp* net, const dmip_mlp* net1, const float* y_dev, int n_y, int xdim, int ydim,
-                 hipStream_t st, StreamScratch& bias_y, dmip::X3Net (&nets)[2]) {
-  nets[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
-  if (net1) nets[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
-  if (int rc = bias_y.alloc((size_t)n_y * net->width * sizeof(float), st)) return rc;
-  dmip::X3BiasPrepParams bp{net->w1, net->b1, y_dev, (float*)bias_y.ptr, net->width, net->in_dim, xdim, ydim};
-  const hipError_t e = dmip::launch_x3_bias_prep(bp, n_y, st);
-  return e == hipSuccess ? DMIP_OK : hip_fail(e, "x3 bias prep launch");
+// what a flow launch needs beside its rows or chains: the images' pointers and the engine's per-y layer-1 data
+// (P: X3FlowParams / X3FlowSampleParams, with the device status word; F32FlowParams / F32FlowSampleParams)
+template <typename P>
+int x3_flow_prep(P& p, StreamScratch& bias_y, const dmip_mlp* net, const dmip_mlp* net1, const float* y_dev, int n_y,
+                 int xdim, int ydim, hipStream_t st) {
+  p.net[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
+  if (net1) p.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
+  p.n_hidden = net->n_hidden;
+  if (int rc = x3_bias_prep(bias_y, net, y_dev, n_y, xdim, ydim, st)) return rc;
+  p.bias_y = (float*)bias_y.ptr;
+  p.err = status_word(dmip::stream_device(st));
+  return p.err ? DMIP_OK : fail(DMIP_ERR_ALLOC, "device status word");
+}
+template <typename P>
+int f32_flow_prep(P& p, StreamScratch& l1y, const dmip_mlp* net, const dmip_mlp* net1, const float* y_dev, int n_y,
+                  int xdim, int ydim, hipStream_t st) {
+  p.net[0] = f32_net(net);
+  if (net1) p.net[1] = f32_net(net1);
+  p.n_hidden = net->n_hidden;
+  if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
+  p.l1y = (float*)l1y.ptr;
+  return DMIP_OK;
+}
+
+// the rows of a log-likelihood launch, whichever engine runs it
+dmip::FlowRows fill_rows(const dmip_vpsde& sde, const float* x_dev, float* logp_out_dev, float* latent_out_dev,
+                         int64_t n, int num_steps) {
+  dmip::FlowRows r{x_dev, logp_out_dev, latent_out_dev, n, num_steps};
+  fill_schedule(sde, num_steps, r.T, r.bmin, r.bdiff, r.h);
+  return r;
+}
+
+// the chains of a flow_sample launch, whichever engine runs it
+dmip::FlowChains fill_chains(const dmip_vpsde& sde, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps,
+                             float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
+                             float* logq_out_dev) {
+  dmip::FlowChains c{x0_dev, x_out_dev, logq_out_dev, n_chains, chain_offset, num_steps};
+  fill_schedule(sde, num_steps, c.T, c.bmin, c.bdiff, c.delta);
+  c.mean = mean;
+  c.stdv = stdv;
+  c.seed = seed;
+  c.base = -0.5 * (double)xdim * 1.8378770664093453 - (double)xdim * std::log((double)stdv);  // log 2 pi
+  return c;
 }
 
 // log p(x | y) along the probability-flow ODE; every argument is validated before any device work
@@ -529,42 +574,20 @@ int flow_logp_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const d
            : dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)))
     return no_kernel("log-likelihood kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
   hipStream_t st = (hipStream_t)stream;
-  auto fill_rows = [&](auto& p) {  // what F32FlowParams and X3FlowParams share
-    p.n_hidden = net->n_hidden;
-    p.x = x_dev;
-    p.logp = logp_out_dev;
-    p.latent = latent_out_dev;
-    p.n = n;
-    p.num_steps = num_steps;
-    fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.h);
-  };
+  if (int rc = x3 ? x3_flow_check("log-likelihood kernel", mode, net, net1, xdim) : DMIP_OK) return rc;
+  if (n == 0) return DMIP_OK;
+  dmip::X3FlowParams px{};  // the selected engine's is filled and launched
+  dmip::F32FlowParams pf{};
+  px.rows = pf.rows = fill_rows(*sde, x_dev, logp_out_dev, latent_out_dev, n, num_steps);
+  StreamScratch per_y;  // the engine's per-y layer-1 bias or image
+  if (int rc = x3 ? x3_flow_prep(px, per_y, net, net1, y_dev, n_y, xdim, ydim, st)
+                  : f32_flow_prep(pf, per_y, net, net1, y_dev, n_y, xdim, ydim, st))
+    return rc;
   bool ok = false;
-  hipError_t e;
-  if (x3) {
-    dmip::X3FlowParams p{};
-    StreamScratch bias_y;
-    if (int rc = x3_flow_check("log-likelihood kernel", mode, net, net1, xdim)) return rc;
-    if (n == 0) return DMIP_OK;
-    if (int rc = x3_flow_prep(net, net1, y_dev, n_y, xdim, ydim, st, bias_y, p.net)) return rc;
-    p.bias_y = (float*)bias_y.ptr;
-    fill_rows(p);
-    p.err = status_word(dmip::stream_device(st));
-    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
-    e = dmip::launch_x3_flow(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
-  } else {
-    if (n == 0) return DMIP_OK;
-    dmip::F32FlowParams p{};
-    p.net[0] = f32_net(net);
-    if (net1) p.net[1] = f32_net(net1);
-    StreamScratch l1y;
-    if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
-    p.l1y = (float*)l1y.ptr;
-    fill_rows(p);
-    e = dmip::launch_f32_flow(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
-  }
+  const hipError_t e = x3 ? dmip::launch_x3_flow(px, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok)
+                          : dmip::launch_f32_flow(pf, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
   if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled log-likelihood kernel");
-  if (e != hipSuccess) return hip_fail(e, "flow_logp launch");
-  return DMIP_OK;
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "flow_logp launch");
 }
 
 // samples of the probability-flow ODE with their log-density; every argument is validated before any device work
@@ -591,45 +614,20 @@ int flow_sample_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const
            : dmip::f32_flow_sample_supported(mode, net->width, net->n_hidden, xdim, ydim)))
     return no_kernel("flow_sample kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
   hipStream_t st = (hipStream_t)stream;
-  auto fill_chains = [&](auto& p) {  // what F32FlowSampleParams and X3FlowSampleParams share
-    p.n_hidden = net->n_hidden;
-    p.x0 = x0_dev;
-    p.x_out = x_out_dev;
-    p.logq = logq_out_dev;
-    p.n = n_chains;
-    p.chain_offset = chain_offset;
-    p.num_steps = num_steps;
-    fill_schedule(*sde, num_steps, p.T, p.bmin, p.bdiff, p.delta);
-    p.mean = mean;
-    p.stdv = stdv;
-    p.seed = seed;
-    p.base = -0.5 * (double)xdim * 1.8378770664093453 - (double)xdim * std::log((double)stdv);  // log 2 pi
-  };
+  if (int rc = x3 ? x3_flow_check("flow_sample kernel", mode, net, net1, xdim) : DMIP_OK) return rc;
+  dmip::X3FlowSampleParams px{};  // the selected engine's is filled and launched
+  dmip::F32FlowSampleParams pf{};
+  px.chains = pf.chains =
+      fill_chains(*sde, xdim, n_chains, chain_offset, num_steps, mean, stdv, seed, x0_dev, x_out_dev, logq_out_dev);
+  StreamScratch per_y;  // the engine's per-y layer-1 bias or image
+  if (int rc = x3 ? x3_flow_prep(px, per_y, net, net1, y_dev, n_y, xdim, ydim, st)
+                  : f32_flow_prep(pf, per_y, net, net1, y_dev, n_y, xdim, ydim, st))
+    return rc;
   bool ok = false;
-  hipError_t e;
-  if (x3) {
-    dmip::X3FlowSampleParams p{};
-    StreamScratch bias_y;
-    if (int rc = x3_flow_check("flow_sample kernel", mode, net, net1, xdim)) return rc;
-    if (int rc = x3_flow_prep(net, net1, y_dev, n_y, xdim, ydim, st, bias_y, p.net)) return rc;
-    p.bias_y = (float*)bias_y.ptr;
-    fill_chains(p);
-    p.err = status_word(dmip::stream_device(st));
-    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
-    e = dmip::launch_x3_flow_sample(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
-  } else {
-    dmip::F32FlowSampleParams p{};
-    p.net[0] = f32_net(net);
-    if (net1) p.net[1] = f32_net(net1);
-    StreamScratch l1y;
-    if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
-    p.l1y = (float*)l1y.ptr;
-    fill_chains(p);
-    e = dmip::launch_f32_flow_sample(p, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
-  }
+  const hipError_t e = x3 ? dmip::launch_x3_flow_sample(px, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok)
+                          : dmip::launch_f32_flow_sample(pf, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
   if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled flow_sample kernel");
-  if (e != hipSuccess) return hip_fail(e, "flow_sample launch");
-  return DMIP_OK;
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "flow_sample launch");
 }
 
 // the tanh chain's answer, as dmip_sampler_supported_precision's
@@ -810,9 +808,7 @@ int dmip_mh_sample_ex(const dmip_surrogate* s, const dmip_scat_noise* noise, con
   dmip::SurrogateParams sp{};
   if (int rc = mh_check(s, noise, sp, y_dev, x_out_dev, n_y, n_chains, chain_offset, num_steps, noise_std)) return rc;
   if (noise_dev || unif_dev) return fail(DMIP_ERR_UNSUPPORTED, "fp32x3 MH: injected draws need DMIP_PREC_F32");
-  if (!s->x3_img)
-    return fail(DMIP_ERR_UNSUPPORTED, "fp32x3 MH: a weight is outside the fp16 range of the split engine (largest |w| " +
-                                          std::to_string(s->x3_range) + " > 65504); use DMIP_PREC_F32");
+  if (!s->x3_img) return x3_range_refused("fp32x3 MH", "|w|", s->x3_range);
   if (n_chains == 0) return DMIP_OK;
   hipStream_t st = (hipStream_t)stream;
   dmip::MhX3Params p{};
@@ -894,9 +890,7 @@ int dmip_dps_sample_ex(const dmip_mlp* prior, const dmip_surrogate* fwd, const d
   }
   if (!prior->dps_l1) return dps_prior_refused();
   if (!prior->dps_x3_img || !fwd->x3_img)
-    return fail(DMIP_ERR_UNSUPPORTED, "fp32x3 DPS: a weight is outside the fp16 range of the split engine (largest |w| " +
-                                          std::to_string(std::max(prior->dps_x3_range, fwd->x3_range)) +
-                                          " > 65504); use DMIP_PREC_F32");
+    return x3_range_refused("fp32x3 DPS", "|w|", std::max(prior->dps_x3_range, fwd->x3_range));
   if (int rc = dps_check_sizes(n_y, n_chains, chain_offset, num_steps, sde, zeta)) return rc;
   if (n_chains == 0) return DMIP_OK;
   hipStream_t st = (hipStream_t)stream;

@@ -9,13 +9,12 @@
 // the fourth column of a quad computes on zeros.
 #pragma once
 #include "dmip_f32.h"
+#include "dmip_flow_rows.h"
 
 namespace dmip {
 namespace f32 {
 
-__device__ __forceinline__ float quad_primal(float v) {  // value of lane 4 (l / 4) (DPP quad_perm 0,0,0,0)
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x00, 0xF, 0xF, true));
-}
+using flow::quad_primal;
 
 // activation of one tile: primal columns tanh (twice on layer 1, nets.py:21-26), tangent columns act'(z_primal) z
 template <bool TWICE>
@@ -98,29 +97,24 @@ __device__ __forceinline__ void flow_score(typename C::E& eng, const int& g, con
     static_assert(C::K1Q1 == C::K1Q0, "the prior's (x, t, bias) columns are the likelihood's");
     out = out + flow_eval<E, C::K1Q1>(eng, 1, L::L1_1, b0, m);  // prior + likelihood
   }
-  const int q0 = j & 12;  // the row's primal column, at g = 0
-  dv = 0.0f;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    a[k] = __shfl(out[k], q0, 64);
-    dv = dv + __shfl(out[k], q0 + 1 + k, 64);
-  }
-  if constexpr (MODE == SAMPLER_POSTERIOR) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) a[k] = cf.g * a[k];
-    dv = cf.g * dv;
-  }
+  flow::gather_score<MODE, D>(out, j, cf, a, dv);
 }
 
-// the static grid of both kernels: at most one resident wave set per y, no more workgroups than 4-row passes
-template <typename K>
-inline unsigned flow_grid_x(K kern, int nw, long long n, int n_y, hipStream_t st) {
-  const long long tiles = (n + 3) / 4;
-  long long g = resident_slots(kern, nw * 64, st) / (n_y > 0 ? n_y : 1);
-  const long long cap = (tiles + nw - 1) / nw;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (unsigned)g;
+// the flow kernels' set-up: layer-1 images (net 0's is the per-y one) and biases into LDS, ring started
+// (f32_flow_kernel calls it; f32_flow_sample_kernel carries the same text, dmip_flow_sample.hip says why)
+template <typename C, int W>
+__device__ __forceinline__ void flow_setup(typename C::E& eng, char* lds, const F32Net (&net)[2], const float* l1y,
+                                           int n_hidden, int yi) {
+  using L = typename C::L;
+  constexpr int NW = Shape<W>::NW, ST = Shape<W>::ST;
+  const int bf = (n_hidden - 1) * W + 16;
+  eng.stage(lds + L::L1_0, (const char*)(l1y + (size_t)yi * ST * C::K1Q0 * 64), ST * C::K1Q0 * 256);
+  if constexpr (C::NNET > 1) eng.stage(lds + L::L1_1, (const char*)net[1].l1, ST * C::K1Q1 * 256);
+  for (int ni = 0; ni < C::NNET; ++ni) {
+    float* bl = (float*)(lds + L::BIAS + ni * L::BIAS_BYTES);
+    for (int i = threadIdx.x; i < bf; i += NW * 64) bl[i] = net[ni].bias[i];
+  }
+  eng.start();
 }
 
 }  // namespace f32

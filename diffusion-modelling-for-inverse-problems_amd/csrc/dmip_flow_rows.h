@@ -1,0 +1,237 @@
+// What the four probability-flow kernels with an exact divergence share whatever engine runs the network
+// (f32_flow_kernel / f32_flow_sample_kernel: dmip_flow.hip, dmip_flow_sample.hip on dmip_flow.h; x3_flow_kernel /
+// x3_flow_sample_kernel: dmip_x3_flow.h): the rows of a wave pass, the two integrators over them, and the launch.
+//
+// A wave pass holds 4 rows x (primal + 3 tangents) in the 16 columns of its B operand, column j = 4 c + m (m = 0 the
+// primal of row c, m = 1..3 the tangent along x_{m-1}); lane = 16 g + j. The kernel supplies the network as a functor
+// score(xt, coef, a, dv) over its engine's flow_score; the drivers own the rounds, the steps and the stores.
+// Everything is always inlined and the functor takes the driver's state by reference: by value, or behind a call, the
+// kernels compiled to other code. The library is built with -ffp-contract=off: the source order of
+// every expression below is its result. One kernel does not go through sample_rows: f32_flow_sample_kernel keeps the
+// same text written out, because its spilling W 512 instantiations measured slower through it (dmip_flow_sample.hip).
+#pragma once
+#include "dmip_device.h"
+#include "dmip_internal.h"
+
+namespace dmip {
+namespace flow {
+
+__device__ __forceinline__ float quad_primal(float v) {  // value of lane 4 (l / 4) (DPP quad_perm 0,0,0,0)
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x00, 0xF, 0xF, true));
+}
+
+// the forward grid of log p(x | y): tau_k = linspace_at(k, S) T (the sampler's schedule, reversed)
+struct FlowCoef {
+  float tau, beta, g;
+};
+__device__ __forceinline__ FlowCoef flow_coef(int k, int S, float T, float bmin, float bdiff) {
+  FlowCoef c;
+  c.tau = __fmul_rn(linspace_at(k, S), T);
+  c.beta = __fadd_rn(bmin, __fmul_rn(bdiff, c.tau));
+  c.g = (float)__dsqrt_rn((double)c.beta);
+  return c;
+}
+
+// The rows of a wave over a static grid: 4 rows per wave pass, NW waves per workgroup, gridDim.x workgroups per y.
+// `rounds` is the same for every wave (one barrier sequence). An idle column (`valid` false: the ragged last pass)
+// reads row 0, computes on zeros and is not stored; stores(): the lane that stores a kept row (its primal column, at
+// g = 0). It reads only the arguments and the grid; the kernels build it before their set-up.
+template <int NW>
+struct Rows {
+  long long n, rounds, row = 0, rr = 0;
+  int w, g, j, m;
+  bool valid = false;
+  __device__ __forceinline__ Rows(long long n_, int w_, int g_, int j_, int m_) : n(n_), w(w_), g(g_), j(j_), m(m_) {
+    const long long tiles = (n + 3) / 4;
+    const long long per_round = (long long)gridDim.x * NW;
+    rounds = (tiles + per_round - 1) / per_round;
+  }
+  __device__ __forceinline__ void seek(long long rd) {
+    row = ((rd * gridDim.x + blockIdx.x) * NW + w) * 4 + (j >> 2);
+    valid = row < n;
+    rr = valid ? row : 0;
+  }
+  __device__ __forceinline__ bool stores() const { return valid && g == 0 && m == 0; }
+};
+
+// a(x, y, tau) of the row on all its lanes, and sum_i da_i/dx_i, from the output tile (rows 4 g + r; the tangent
+// column 1 + i carries row i's derivative); cf.g: the Posterior estimator's factor on a and on its divergence
+// (nets.py:155-157). The scaling of a keeps the fp32x3 kernels' form, __fmul_rn(cf.g, a[k]); the exact-f32 flow_score
+// wrote cf.g * a[k], the same single rounded multiply (HIP's __fmul_rn is the plain operator, and nothing is
+// contracted).
+template <int MODE, int D, typename V, typename Coef>
+__device__ __forceinline__ void gather_score(const V& out, const int& j, const Coef& cf, float (&a)[D], float& dv) {
+  const int q0 = j & 12;  // the row's primal column, at g = 0
+  dv = 0.0f;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    a[k] = __shfl(out[k], q0, 64);
+    dv = dv + __shfl(out[k], q0 + 1 + k, 64);
+  }
+  if constexpr (MODE == SAMPLER_POSTERIOR) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) a[k] = __fmul_rn(cf.g, a[k]);
+    dv = cf.g * dv;
+  }
+}
+
+// ---------------------------------------------------------------------------- log p(x | y)
+// Forward grid, h = T / S, and for a row x_0 = x
+//   v(x, tau)    = -1/2 beta(tau) x - 1/2 g(tau) a(x, y, tau)                 (= -mu(T - tau, x, y, lmbd = 1))
+//   divv(x, tau) = -1/2 beta(tau) d - 1/2 g(tau) sum_i da_i/dx_i
+// integrated with Heun's explicit trapezoid, k = 0..S-1:
+//   k1 = v(x_k, tau_k), x~ = x_k + h k1, k2 = v(x~, tau_{k+1}), x_{k+1} = x_k + (h/2)(k1 + k2)
+//   I += (h/2)(divv(x_k, tau_k) + divv(x~, tau_{k+1}))                        (f64: 2S terms)
+//   log p(x | y) = -(d/2) log 2 pi - 1/2 |x_S|^2 + I
+// `nonfinite` is ORed with "a kept row's I is not finite" (the fp32x3 engine: a tangent beyond the split's range).
+template <int D, int NW, typename Score>
+__device__ __forceinline__ void logp_rows(const FlowRows& p, Rows<NW>& rows, int yi, bool& nonfinite, Score&& score) {
+  const int S = p.num_steps;
+  const float hh = __fmul_rn(0.5f, p.h);
+  for (long long rd = 0; rd < rows.rounds; ++rd) {
+    rows.seek(rd);
+    float x[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const float xv = p.x[((size_t)yi * p.n + rows.rr) * D + k];
+      x[k] = rows.valid ? xv : 0.0f;  // idle columns compute on zeros and are not stored
+    }
+    double I = 0.0;
+    for (int k = 0; k < S; ++k) {
+      float k1[D], xt[D], d1 = 0.0f;
+#pragma unroll
+      for (int i = 0; i < D; ++i) xt[i] = x[i];
+      // stage 0: k1 and divv at (x_k, tau_k); stage 1: k2 and divv at (x~, tau_{k+1}) -- one copy of the network code
+#pragma unroll 1
+      for (int stage = 0; stage < 2; ++stage) {
+        const FlowCoef cf = flow_coef(k + stage, S, p.T, p.bmin, p.bdiff);
+        float a[D], dv;
+        score(xt, cf, a, dv);
+        const float dd = -(0.5f * cf.beta * (float)D + 0.5f * cf.g * dv);
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+          const float kv = -(0.5f * cf.g * a[i] + 0.5f * cf.beta * xt[i]);
+          if (stage == 0) {
+            k1[i] = kv;
+            xt[i] = x[i] + p.h * kv;
+          } else {
+            x[i] = x[i] + hh * (k1[i] + kv);
+          }
+        }
+        if (stage == 0) d1 = dd;
+        else I += (double)hh * ((double)d1 + (double)dd);
+      }
+    }
+    nonfinite |= rows.valid && !__builtin_isfinite(I);
+    if (rows.stores()) {
+      double r2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) r2 += (double)x[i] * (double)x[i];
+      const size_t o = (size_t)yi * p.n + rows.row;
+      p.logp[o] = (float)(-0.5 * (double)D * 1.8378770664093453 - 0.5 * r2 + I);  // log 2 pi
+      if (p.latent) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) p.latent[o * D + i] = x[i];
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------- samples with their log-density
+// Reverse grid of the samplers: tau_i, beta_i, g_i = step_coef(i, S, ...) at lmbd = 1 for i = 0..S, delta = T / S. A
+// chain starts at x_0 = mean + std n (the first normals of its stream (seed, chain_offset + row, y index), as every
+// sampler) or at row [y][row] of the caller's x0, and for i = 0..S-1
+//   k1 = m(x_i, i), x~ = fl(x_i + fl(delta k1)), k2 = m(x~, i + 1), x_{i+1} = fl(x_i + fl(fl(delta/2) fl(k1 + k2)))
+//   dm(x, i) = 1/2 g_i sum_j da_j/dx_j (x, y, tau_i) + 1/2 beta_i d           (the divergence of m(., i))
+//   J += (delta/2) (dm(x_i, i) + dm(x~, i + 1))                                (f64: 2S terms)
+//   log q(x_S | y) = -(d/2) log 2 pi - d log std - 1/2 |(x_0 - mean) / std|^2 - J
+// m is HeunStep::slope, so x_S is the Heun sampler's x_S. The base term is folded into the f64 accumulator before the
+// step loop: only x and the accumulator live across it. `nonfinite` as logp_rows'.
+template <int D, int NW, typename Score>
+__device__ __forceinline__ void sample_rows(const FlowChains& p, Rows<NW>& rows, int yi, bool& nonfinite,
+                                            Score&& score) {
+  const int S = p.num_steps;
+  const float hd = __fmul_rn(0.5f, p.delta);
+  for (long long rd = 0; rd < rows.rounds; ++rd) {
+    rows.seek(rd);
+    float x[D];
+    if (p.x0) {
+      const float* src = p.x0 + ((size_t)yi * p.n + rows.rr) * D;
+#pragma unroll
+      for (int k = 0; k < D; ++k) x[k] = src[k];
+    } else {
+      Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + rows.rr), (uint64_t)yi);
+      float n0[D];
+      rng_normals<D>(rng, n0);
+#pragma unroll
+      for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+    }
+    // acc = log N(x_0; mean, std^2 I) - J, from the f32 x_0 whichever way it came
+    double acc = p.base;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double z = ((double)x[k] - (double)p.mean) / (double)p.stdv;
+      acc -= 0.5 * z * z;
+      x[k] = rows.valid ? x[k] : 0.0f;  // idle columns compute on zeros and are not stored
+    }
+    for (int i = 0; i < S; ++i) {
+      float k1[D], xt[D], d1 = 0.0f;
+#pragma unroll
+      for (int k = 0; k < D; ++k) xt[k] = x[k];
+      // stage 0: k1 and dm at (x_i, i); stage 1: k2 and dm at (x~, i + 1) -- one copy of the network code
+#pragma unroll 1
+      for (int stage = 0; stage < 2; ++stage) {
+        const StepCoef c = step_coef(i + stage, S, p.T, p.bmin, p.bdiff, 0.5f, 0.0f);  // lmbd = 1: g_mu = fl(0.5 g)
+        float a[D], dv;
+        score(xt, c, a, dv);
+        const float dd = 0.5f * c.g * dv + 0.5f * c.beta * (float)D;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float mk = HeunStep::slope(xt[k], a[k], c);
+          if (stage == 0) {
+            k1[k] = mk;
+            xt[k] = HeunStep::predict(x[k], mk, p.delta);
+          } else {
+            x[k] = HeunStep::correct(x[k], k1[k], mk, p.delta);
+          }
+        }
+        if (stage == 0) d1 = dd;
+        else acc -= (double)hd * ((double)d1 + (double)dd);
+      }
+    }
+    nonfinite |= rows.valid && !__builtin_isfinite(acc);
+    if (rows.stores()) {
+      const size_t o = (size_t)yi * p.n + rows.row;
+      p.logq[o] = (float)acc;
+#pragma unroll
+      for (int k = 0; k < D; ++k) p.x_out[o * D + k] = x[k];
+    }
+  }
+}
+
+}  // namespace flow
+
+// ----------------------------------------------------------------- launch helpers (per TU)
+// the static grid of the four kernels: at most one resident wave set per y, no more workgroups than 4-row passes
+template <typename K>
+inline unsigned flow_grid_x(K kern, int nw, long long n, int n_y, hipStream_t st) {
+  const long long tiles = (n + 3) / 4;
+  long long g = resident_slots(kern, nw * 64, st) / (n_y > 0 ? n_y : 1);
+  const long long cap = (tiles + nw - 1) / nw;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+// n: the rows (chains) per y of p
+template <typename K, typename P>
+inline hipError_t flow_launch(K kern, int nw, const P& p, long long n, int n_y, hipStream_t st) {
+  const unsigned g = flow_grid_x(kern, nw, n, n_y, st);
+  hipLaunchKernelGGL(kern, dim3(g, (unsigned)n_y), dim3(nw * 64), 0, st, p);
+  return hipGetLastError();
+}
+
+// the (width, xdim) pairs every dispatcher compiles: X(width, xdim) per shape
+#define DMIP_FLOW_SHAPES(X) X(64, 2) X(128, 2) X(256, 2) X(512, 2) X(64, 3) X(128, 3) X(256, 3) X(512, 3)
+
+}  // namespace dmip

@@ -300,18 +300,33 @@ struct F32L1PrepParams {
   int width, in_dim, xdim, ydim, k1q;
 };
 
-// log p(x | y) along the probability-flow ODE (dmip_flow.hip): Heun steps on the forward time grid, the divergence
-// from forward tangents (4 rows x (primal + 3 tangents) per wave pass)
-struct F32FlowParams {
-  F32Net net[2];              // net 0: CDE / likelihood; net 1: the Posterior prior
-  const float* l1y;           // per-y layer-1 images [n_y][W/16][K1Q][64] (y folded in)
-  int n_hidden;
+// what the row drivers of the probability-flow kernels read (dmip_flow_rows.h), whatever engine runs the network
+struct FlowRows {             // log p(x | y) of given rows
   const float* x;             // [n_y][n][D]
   float* logp;                // [n_y][n]
   float* latent;              // [n_y][n][D] x_S, or null
   long long n;                // rows per y
   int num_steps;
   float T, bmin, bdiff, h;    // h = T / num_steps
+};
+struct FlowChains {           // samples with their log-density
+  const float* x0;            // start states [n_y][n][D] or null (randn stdv + mean from the RNG)
+  float* x_out;               // [n_y][n][D]
+  float* logq;                // [n_y][n]
+  long long n, chain_offset;  // chains per y; the RNG's chain index of row 0
+  int num_steps;
+  float T, bmin, bdiff, delta, mean, stdv;
+  unsigned long long seed;
+  double base;                // -(D/2) log 2 pi - D log stdv
+};
+
+// log p(x | y) along the probability-flow ODE (dmip_flow.hip): Heun steps on the forward time grid, the divergence
+// from forward tangents (4 rows x (primal + 3 tangents) per wave pass)
+struct F32FlowParams {
+  F32Net net[2];              // net 0: CDE / likelihood; net 1: the Posterior prior
+  const float* l1y;           // per-y layer-1 images [n_y][W/16][K1Q][64] (y folded in)
+  int n_hidden;
+  FlowRows rows;
 };
 hipError_t launch_f32_flow(const F32FlowParams& p, int mode, int width, int n_hidden, int xdim, int ydim, int n_y,
                            hipStream_t st, bool* supported);
@@ -323,14 +338,7 @@ struct F32FlowSampleParams {
   F32Net net[2];              // net 0: CDE / likelihood; net 1: the Posterior prior
   const float* l1y;           // per-y layer-1 images [n_y][W/16][K1Q][64] (y folded in)
   int n_hidden;
-  const float* x0;            // start states [n_y][n][D] or null (randn stdv + mean from the RNG)
-  float* x_out;               // [n_y][n][D]
-  float* logq;                // [n_y][n]
-  long long n, chain_offset;  // chains per y; the RNG's chain index of row 0
-  int num_steps;
-  float T, bmin, bdiff, delta, mean, stdv;
-  unsigned long long seed;
-  double base;                // -(D/2) log 2 pi - D log stdv
+  FlowChains chains;
 };
 hipError_t launch_f32_flow_sample(const F32FlowSampleParams& p, int mode, int width, int n_hidden, int xdim, int ydim,
                                   int n_y, hipStream_t st, bool* supported);
@@ -421,26 +429,14 @@ struct X3FlowParams {
   X3Net net[2];               // net 0: CDE / likelihood; net 1: the Posterior prior
   const float* bias_y;        // per-y layer-1 bias c (b1 + W1_y y) [n_y][W]
   int n_hidden;
-  const float* x;             // [n_y][n][D]
-  float* logp;                // [n_y][n]
-  float* latent;              // [n_y][n][D] x_S, or null
-  long long n;                // rows per y
-  int num_steps;
-  float T, bmin, bdiff, h;    // h = T / num_steps
+  FlowRows rows;
   unsigned int* err;
 };
 struct X3FlowSampleParams {
   X3Net net[2];
   const float* bias_y;
   int n_hidden;
-  const float* x0;            // start states [n_y][n][D] or null (randn stdv + mean from the RNG)
-  float* x_out;               // [n_y][n][D]
-  float* logq;                // [n_y][n]
-  long long n, chain_offset;  // chains per y; the RNG's chain index of row 0
-  int num_steps;
-  float T, bmin, bdiff, delta, mean, stdv;
-  unsigned long long seed;
-  double base;                // -(D/2) log 2 pi - D log stdv
+  FlowChains chains;
   unsigned int* err;
 };
 // CDE and Posterior, xdim 2 or 3, any ydim, 1 to 3 hidden layers, widths 64 / 128 / 256 / 512 (dmip_x3_flow.hip)

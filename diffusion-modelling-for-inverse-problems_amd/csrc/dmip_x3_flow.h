@@ -19,6 +19,7 @@
 // r of the primal is re-activated from the quad's primal pre-activation (one DPP move), as dmip_flow.h's flow_act; dr
 // is split into (hi, lo) fp16 like any activation.
 #pragma once
+#include "dmip_flow_rows.h"
 #include "dmip_x3.h"
 
 namespace dmip {
@@ -26,9 +27,7 @@ namespace x3 {
 
 constexpr float kLn2 = 0.69314718055994531f;
 
-__device__ __forceinline__ float quad_primal(float v) {  // value of lane 4 (l / 4) (DPP quad_perm 0,0,0,0)
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x00, 0xF, 0xF, true));
-}
+using flow::quad_primal;
 
 // activate tile o into the (hi, lo) B operands of the next layer: primal columns r (XEngine::act_store's values),
 // tangent columns dr
@@ -179,18 +178,7 @@ __device__ __forceinline__ void flow_score(typename C::E& eng, const int& g, con
   }
   f32x4 out = flow_eval<C>(eng, m, 0, b1);
   if constexpr (C::NNET > 1) out = out + flow_eval<C>(eng, m, 1, b1);  // likelihood + prior
-  const int q0 = j & 12;  // the row's primal column, at g = 0
-  dv = 0.0f;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    a[k] = __shfl(out[k], q0, 64);
-    dv = dv + __shfl(out[k], q0 + 1 + k, 64);
-  }
-  if constexpr (MODE == SAMPLER_POSTERIOR) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) a[k] = __fmul_rn(cf.g, a[k]);
-    dv = cf.g * dv;
-  }
+  flow::gather_score<MODE, D>(out, j, cf, a, dv);
 }
 
 // the sampler kernel's set-up: layer-1 images and biases into LDS (net 0's layer-1 bias is the per-y one), ring started
@@ -215,25 +203,13 @@ __device__ __forceinline__ void flow_setup(typename C::E& eng, char* lds, const 
   eng.start();
 }
 
-// ---------------------------------------------------------------------------- log p(x | y)
-// dmip_flow.hip's scheme: the forward grid tau_k = linspace_at(k, S) T, Heun, an f64 sum of 2S divergence terms
-struct FlowCoef {
-  float tau, beta, g;
-};
-__device__ __forceinline__ FlowCoef flow_coef(int k, int S, float T, float bmin, float bdiff) {
-  FlowCoef c;
-  c.tau = __fmul_rn(linspace_at(k, S), T);
-  c.beta = __fadd_rn(bmin, __fmul_rn(bdiff, c.tau));
-  c.g = (float)__dsqrt_rn((double)c.beta);
-  return c;
-}
-
+// log p(x | y): dmip_flow_rows.h's logp_rows (dmip_flow.hip's scheme) over this engine's flow_score. `oor` collects a
+// kept row's layer-1 input outside the split's range and a tangent beyond it (a non-finite accumulator)
 template <int MODE, int W, int D>
 __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_flow_kernel(X3FlowParams p) {
   using C = SamplerCfg<MODE, W, D, 0, 0>;
   using L = typename C::L;
   using E = typename C::E;
-  constexpr int NW = Shape<W>::NW;
   static_assert(L::TOTAL <= kLdsBudget, "LDS budget");
   static_assert(D <= 3, "a quad holds the primal and at most 3 tangents");
   __shared__ __attribute__((aligned(16))) char lds[L::TOTAL];
@@ -245,77 +221,25 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_flow_k
   E eng{lds, {p.net[0].stream, p.net[1].stream}, {L::L1, L::L1 + L::L1_BYTES}, {L::BIAS, L::BIAS + L::BIAS_BYTES}};
   eng.w = w, eng.lane = lane, eng.g = g;
   eng.init(p.n_hidden);
+  flow::Rows<Shape<W>::NW> rows(p.rows.n, w, g, j, m);
   flow_setup<C, W>(eng, lds, p.net, p.bias_y, p.n_hidden, yi);
 
-  const int S = p.num_steps;
-  const long long tiles = (p.n + 3) / 4;  // 4 rows per wave pass
-  const long long per_round = (long long)gridDim.x * NW;
-  const long long rounds = (tiles + per_round - 1) / per_round;  // the same for every wave: one barrier sequence
-  const float hh = __fmul_rn(0.5f, p.h);
   bool oor = false;
-
-  for (long long rd = 0; rd < rounds; ++rd) {
-    const long long row = ((rd * gridDim.x + blockIdx.x) * NW + w) * 4 + (j >> 2);
-    const bool valid = row < p.n;
-    const long long rr = valid ? row : 0;
-    float x[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const float xv = p.x[((size_t)yi * p.n + rr) * D + k];
-      x[k] = valid ? xv : 0.0f;  // idle columns compute on zeros and are not stored
-    }
-    double I = 0.0;
-    for (int k = 0; k < S; ++k) {
-      float k1[D], xt[D], d1 = 0.0f;
-#pragma unroll
-      for (int i = 0; i < D; ++i) xt[i] = x[i];
-      // stage 0: k1 and divv at (x_k, tau_k); stage 1: k2 and divv at (x~, tau_{k+1}) -- one copy of the network code
-#pragma unroll 1
-      for (int stage = 0; stage < 2; ++stage) {
-        const FlowCoef cf = flow_coef(k + stage, S, p.T, p.bmin, p.bdiff);
-        float a[D], dv;
-        flow_score<C, MODE, D>(eng, g, j, m, xt, cf, valid, oor, a, dv);
-        const float dd = -(0.5f * cf.beta * (float)D + 0.5f * cf.g * dv);
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-          const float kv = -(0.5f * cf.g * a[i] + 0.5f * cf.beta * xt[i]);
-          if (stage == 0) {
-            k1[i] = kv;
-            xt[i] = x[i] + p.h * kv;
-          } else {
-            x[i] = x[i] + hh * (k1[i] + kv);
-          }
-        }
-        if (stage == 0) d1 = dd;
-        else I += (double)hh * ((double)d1 + (double)dd);
-      }
-    }
-    oor |= valid && !__builtin_isfinite(I);  // a tangent beyond the split's range
-    if (valid && g == 0 && m == 0) {
-      double r2 = 0.0;
-#pragma unroll
-      for (int i = 0; i < D; ++i) r2 += (double)x[i] * (double)x[i];
-      const size_t o = (size_t)yi * p.n + row;
-      p.logp[o] = (float)(-0.5 * (double)D * 1.8378770664093453 - 0.5 * r2 + I);  // log 2 pi
-      if (p.latent) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) p.latent[o * D + i] = x[i];
-      }
-    }
-  }
+  flow::logp_rows<D>(p.rows, rows, yi, oor,
+                     [&](const float (&xt)[D], const flow::FlowCoef& cf, float (&a)[D], float& dv)
+                         __attribute__((always_inline)) {
+                           flow_score<C, MODE, D>(eng, g, j, m, xt, cf, rows.valid, oor, a, dv);
+                         });
   eng.finish();
   report_range(oor, p.err, lane);
 }
 
-// ---------------------------------------------------------------------------- samples with their log-density
-// dmip_flow_sample.hip's scheme: the Heun sampler's steps (dmip_device.h HeunStep, its rounding order) with the
-// divergence of the drift beside them; the base density is folded into the f64 accumulator before the step loop
+// samples with their log-density: dmip_flow_rows.h's sample_rows (dmip_flow_sample.hip's scheme); `oor` as above
 template <int MODE, int W, int D>
 __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_flow_sample_kernel(X3FlowSampleParams p) {
   using C = SamplerCfg<MODE, W, D, 0, 0>;
   using L = typename C::L;
   using E = typename C::E;
-  constexpr int NW = Shape<W>::NW;
   static_assert(L::TOTAL <= kLdsBudget, "LDS budget");
   static_assert(D <= 3, "a quad holds the primal and at most 3 tangents");
   __shared__ __attribute__((aligned(16))) char lds[L::TOTAL];
@@ -327,108 +251,20 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_flow_s
   E eng{lds, {p.net[0].stream, p.net[1].stream}, {L::L1, L::L1 + L::L1_BYTES}, {L::BIAS, L::BIAS + L::BIAS_BYTES}};
   eng.w = w, eng.lane = lane, eng.g = g;
   eng.init(p.n_hidden);
+  flow::Rows<Shape<W>::NW> rows(p.chains.n, w, g, j, m);
   flow_setup<C, W>(eng, lds, p.net, p.bias_y, p.n_hidden, yi);
 
-  const int S = p.num_steps;
-  const long long tiles = (p.n + 3) / 4;  // 4 rows per wave pass
-  const long long per_round = (long long)gridDim.x * NW;
-  const long long rounds = (tiles + per_round - 1) / per_round;  // the same for every wave: one barrier sequence
-  const float hd = __fmul_rn(0.5f, p.delta);
   bool oor = false;
-
-  for (long long rd = 0; rd < rounds; ++rd) {
-    const long long row = ((rd * gridDim.x + blockIdx.x) * NW + w) * 4 + (j >> 2);
-    const bool valid = row < p.n;
-    const long long rr = valid ? row : 0;
-    float x[D];
-    if (p.x0) {
-      const float* src = p.x0 + ((size_t)yi * p.n + rr) * D;
-#pragma unroll
-      for (int k = 0; k < D; ++k) x[k] = src[k];
-    } else {
-      Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + rr), (uint64_t)yi);
-      float n0[D];
-      rng_normals<D>(rng, n0);
-#pragma unroll
-      for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
-    }
-    // acc = log N(x_0; mean, std^2 I) - J, from the f32 x_0 whichever way it came
-    double acc = p.base;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double z = ((double)x[k] - (double)p.mean) / (double)p.stdv;
-      acc -= 0.5 * z * z;
-      x[k] = valid ? x[k] : 0.0f;  // idle columns compute on zeros and are not stored
-    }
-    for (int i = 0; i < S; ++i) {
-      float k1[D], xt[D], d1 = 0.0f;
-#pragma unroll
-      for (int k = 0; k < D; ++k) xt[k] = x[k];
-      // stage 0: k1 and dm at (x_i, i); stage 1: k2 and dm at (x~, i + 1) -- one copy of the network code
-#pragma unroll 1
-      for (int stage = 0; stage < 2; ++stage) {
-        const StepCoef c = step_coef(i + stage, S, p.T, p.bmin, p.bdiff, 0.5f, 0.0f);  // lmbd = 1: g_mu = fl(0.5 g)
-        float a[D], dv;
-        flow_score<C, MODE, D>(eng, g, j, m, xt, c, valid, oor, a, dv);
-        const float dd = 0.5f * c.g * dv + 0.5f * c.beta * (float)D;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          const float mk = HeunStep::slope(xt[k], a[k], c);
-          if (stage == 0) {
-            k1[k] = mk;
-            xt[k] = HeunStep::predict(x[k], mk, p.delta);
-          } else {
-            x[k] = HeunStep::correct(x[k], k1[k], mk, p.delta);
-          }
-        }
-        if (stage == 0) d1 = dd;
-        else acc -= (double)hd * ((double)d1 + (double)dd);
-      }
-    }
-    oor |= valid && !__builtin_isfinite(acc);  // a tangent beyond the split's range
-    if (valid && g == 0 && m == 0) {
-      const size_t o = (size_t)yi * p.n + row;
-      p.logq[o] = (float)acc;
-#pragma unroll
-      for (int k = 0; k < D; ++k) p.x_out[o * D + k] = x[k];
-    }
-  }
+  flow::sample_rows<D>(p.chains, rows, yi, oor,
+                       [&](const float (&xt)[D], const StepCoef& c, float (&a)[D], float& dv)
+                           __attribute__((always_inline)) {
+                             flow_score<C, MODE, D>(eng, g, j, m, xt, c, rows.valid, oor, a, dv);
+                           });
   eng.finish();
   report_range(oor, p.err, lane);
 }
 
 }  // namespace x3
-
-// ----------------------------------------------------------------- launch helpers (per TU)
-// the static grid of both kernels (dmip_flow.h's): at most one resident wave set per y, no more workgroups than
-// 4-row passes
-template <typename K>
-inline unsigned x3_flow_grid_x(K kern, int nw, long long n, int n_y, hipStream_t st) {
-  const long long tiles = (n + 3) / 4;
-  long long g = resident_slots(kern, nw * 64, st) / (n_y > 0 ? n_y : 1);
-  const long long cap = (tiles + nw - 1) / nw;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-template <int MODE, int W, int D>
-inline hipError_t launch_x3_flow_t(const X3FlowParams& p, int n_y, hipStream_t st) {
-  constexpr int NW = x3::Shape<W>::NW;
-  auto kern = x3::x3_flow_kernel<MODE, W, D>;
-  const unsigned g = x3_flow_grid_x(kern, NW, p.n, n_y, st);
-  hipLaunchKernelGGL(kern, dim3(g, (unsigned)n_y), dim3(NW * 64), 0, st, p);
-  return hipGetLastError();
-}
-
-template <int MODE, int W, int D>
-inline hipError_t launch_x3_flow_sample_t(const X3FlowSampleParams& p, int n_y, hipStream_t st) {
-  constexpr int NW = x3::Shape<W>::NW;
-  auto kern = x3::x3_flow_sample_kernel<MODE, W, D>;
-  const unsigned g = x3_flow_grid_x(kern, NW, p.n, n_y, st);
-  hipLaunchKernelGGL(kern, dim3(g, (unsigned)n_y), dim3(NW * 64), 0, st, p);
-  return hipGetLastError();
-}
 
 // per-mode instantiations (dmip_x3_flow_{cde,post}.hip, dmip_x3_flow_sample_{cde,post}.hip)
 hipError_t launch_x3_flow_cde(const X3FlowParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);

@@ -7,8 +7,9 @@ namespace dmip {
 hipError_t launch_x3_flow_post(const X3FlowParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok) {
   *ok = true;
 #define X(Wv, Dv) \
-  if (width == Wv && xdim == Dv) return launch_x3_flow_t<SAMPLER_POSTERIOR, Wv, Dv>(p, n_y, st);
-  X(64, 2) X(128, 2) X(256, 2) X(512, 2) X(64, 3) X(128, 3) X(256, 3) X(512, 3)
+  if (width == Wv && xdim == Dv) \
+    return flow_launch(x3::x3_flow_kernel<SAMPLER_POSTERIOR, Wv, Dv>, x3::Shape<Wv>::NW, p, p.rows.n, n_y, st);
+  DMIP_FLOW_SHAPES(X)
 #undef X
   *ok = false;
   return hipSuccess;

@@ -8,8 +8,10 @@ hipError_t launch_x3_flow_sample_post(const X3FlowSampleParams& p, int width, in
                                       bool* ok) {
   *ok = true;
 #define X(Wv, Dv) \
-  if (width == Wv && xdim == Dv) return launch_x3_flow_sample_t<SAMPLER_POSTERIOR, Wv, Dv>(p, n_y, st);
-  X(64, 2) X(128, 2) X(256, 2) X(512, 2) X(64, 3) X(128, 3) X(256, 3) X(512, 3)
+  if (width == Wv && xdim == Dv) \
+    return flow_launch(x3::x3_flow_sample_kernel<SAMPLER_POSTERIOR, Wv, Dv>, x3::Shape<Wv>::NW, p, p.chains.n, n_y, \
+                       st);
+  DMIP_FLOW_SHAPES(X)
 #undef X
   *ok = false;
   return hipSuccess;

@@ -15,11 +15,9 @@ import torch
 
 import flow_ref as FR
 import oracle as O
-from conftest import state_from_npz
+from flow_gpu import DEV, gate, lin, post, scat, seeded
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -28,35 +26,12 @@ def _need_gpu():
         pytest.skip("no HIP device")
 
 
-def _load_linear(net, params):
-    lins = [m for m in net if isinstance(m, torch.nn.Linear)]
-    assert len(lins) == len(params)
-    with torch.no_grad():
-        for lin, (W, b) in zip(lins, params):
-            lin.weight.copy_(torch.from_numpy(W))
-            lin.bias.copy_(torch.from_numpy(b))
-
-
 def _gate(name, got, ref64, ref32):
-    e_gpu = np.abs(got - ref64).max()
-    e_cpu = np.abs(ref32 - ref64).max()
-    print(f"{name}: e_gpu = {e_gpu:.3e}, e_cpu = {e_cpu:.3e}, e_gpu / e_cpu = {e_gpu / e_cpu:.2f}")
-    assert np.all(np.isfinite(got))
-    assert e_gpu <= 4 * e_cpu + 1e-6, (name, e_gpu, e_cpu)
+    gate(name, got, ref64, ref32, scaled=False)  # |logp| and |x_S| are O(1) here: the additive term is 1e-6
 
 
 def _fixture_model(dmip, golden, case):
-    if case in ("a", "c"):
-        m = dmip.CDE(2, 2, [64] * 3)
-        m.sde.a.load_state_dict(state_from_npz(golden("ckpt_lin.npz")))
-    elif case == "b":
-        m = dmip.CDE(3, 23, [256] * 3)
-        m.sde.a.load_state_dict(state_from_npz(golden("ckpt_scat.npz")))
-    else:
-        m = dmip.PosteriorDiffusionEstimator(3, 23, [256] * 3)
-        m.sde.a.prior_net.load_state_dict(state_from_npz(golden("ckpt_prior_scat.npz")))
-        m.sde.a.likelihood_net.load_state_dict(state_from_npz(golden("posterior_loss.npz"), "lik_"))
-    return m
+    return {"a": lin, "c": lin, "b": scat, "d": post}[case](dmip, golden)
 
 
 @pytest.mark.parametrize("case", ["a", "b", "d"])
@@ -90,9 +65,7 @@ def _seeded(dmip, name):
     """(model, x (n, d), ys (3, ydim), S, per-y (logp_f64, latent_f64, logp_f32, latent_f32)) -- the reference is
     computed once per shape and shared, unchanged, by the tests that slice it."""
     W, NL, xd, yd, n, S, seed = SHAPES[name]
-    params = O.reference_weights([xd + yd + 1] + [W] * NL + [xd], seed)
-    m = dmip.CDE(xd, yd, [W] * NL)
-    _load_linear(m.sde.a, params)
+    m, params = seeded(dmip, W, NL, xd, yd, seed)
     if name not in _refs:
         g = np.random.default_rng(seed)
         x = g.normal(size=(n, xd)).astype(np.float32)

@@ -21,12 +21,12 @@ import torch
 import flow_ref as FR
 import flow_sample_ref as FS
 import heun_ref as HR
-import oracle as O
-from conftest import state_from_npz
+from flow_gpu import DEV, gate, seeded
+from flow_gpu import bits as _bits, dev as _dev, device_x0 as _device_x0, sample_reference as _sample_reference
+from flow_gpu import lin as _lin, post as _post, scat as _scat
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 K = 4
 X3 = "fp32x3"
 
@@ -42,52 +42,8 @@ def ev(dmip):
     return importlib.import_module(dmip.__name__ + ".evaluate")
 
 
-def _bits(t):
-    return t.detach().cpu().contiguous().numpy().view(np.uint32)
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a)).to(DEV)  # (a copy: the shared references are read-only)
-
-
 def _gate(name, got, ref64, ref32):
-    got, ref64, ref32 = (np.asarray(v, np.float64) for v in (got, ref64, ref32))
-    e_gpu = np.abs(got - ref64).max()
-    e_cpu = np.abs(ref32 - ref64).max()
-    tol = K * e_cpu + 1e-6 * max(1.0, np.abs(ref64).max())
-    print(f"X3GATE {name}: e_gpu = {e_gpu:.3e}, e_cpu = {e_cpu:.3e}, e_gpu / e_cpu = {e_gpu / max(e_cpu, 1e-300):.2f}, "
-          f"max |ref| = {np.abs(ref64).max():.4g}, tol = {tol:.3e}")
-    assert np.all(np.isfinite(got))
-    assert e_gpu <= tol, (name, e_gpu, e_cpu, tol)
-
-
-def _lin(dmip, golden):
-    m = dmip.CDE(2, 2, [64] * 3)
-    m.sde.a.load_state_dict(state_from_npz(golden("ckpt_lin.npz")))
-    return m
-
-
-def _scat(dmip, golden):
-    m = dmip.CDE(3, 23, [256] * 3)
-    m.sde.a.load_state_dict(state_from_npz(golden("ckpt_scat.npz")))
-    return m
-
-
-def _post(dmip, golden):
-    m = dmip.PosteriorDiffusionEstimator(3, 23, [256] * 3)
-    m.sde.a.prior_net.load_state_dict(state_from_npz(golden("ckpt_prior_scat.npz")))
-    m.sde.a.likelihood_net.load_state_dict(state_from_npz(golden("posterior_loss.npz"), "lik_"))
-    return m
-
-
-def _sample_reference(params, x0, y, S, prior=None):
-    """((x_f64, logq_f64), (x_f32, logq_f32)) of the restatement, read-only."""
-    out = []
-    for dtype in (np.float64, np.float32):
-        x, lq = FS.sample_with_logq(params, x0, y, S, prior, dtype=dtype)
-        x.setflags(write=False), lq.setflags(write=False)
-        out.append((x, lq))
-    return out
+    gate(name, got, ref64, ref32, k=K, tag="X3GATE ")
 
 
 # ------------------------------------------------------------------------------------- 1. fixture checkpoints
@@ -149,23 +105,12 @@ S_SEEDED = 4
 _refs = {}
 
 
-def _load_linear(net, params):
-    lins = [m for m in net if isinstance(m, torch.nn.Linear)]
-    assert len(lins) == len(params)
-    with torch.no_grad():
-        for lin, (W, b) in zip(lins, params):
-            lin.weight.copy_(torch.from_numpy(W))
-            lin.bias.copy_(torch.from_numpy(b))
-
-
 def _seeded(dmip, name):
     """(model, rows x (n, d) -- of log_prob, and the x0 of sample_with_log_prob --, ys (3, ydim), per-y references
     {"logp": (l64, z64, l32, z32), "sample": ((x64, q64), (x32, q32))}) -- computed once per shape, shared,
     unchanged."""
     W, NL, xd, yd, n, seed = SHAPES[name]
-    params = O.reference_weights([xd + yd + 1] + [W] * NL + [xd], seed)
-    m = dmip.CDE(xd, yd, [W] * NL)
-    _load_linear(m.sde.a, params)
+    m, params = seeded(dmip, W, NL, xd, yd, seed)
     if name not in _refs:
         ys = np.random.default_rng(seed).normal(size=(3, yd)).astype(np.float32)
         n_y = 3 if name == "w64" else 1
@@ -241,16 +186,6 @@ def test_same_x_as_the_fp32x3_heun_sampler(dmip, golden, case):
 
 
 # ------------------------------------------------------------------------------------- 3. bitwise invariances
-def _device_x0(dmip, seed, offset, stream, n, xd, mean=0.0, std=1.0):
-    """mean + std times the first xd normals of each chain's stream, from the device's own generator."""
-    pairs = (xd + 1) // 2
-    out = torch.empty(n, 2 * pairs, device=DEV, dtype=torch.float32)
-    dmip._lib.rng_normals(seed, offset, stream, n, pairs, out)
-    torch.cuda.synchronize()
-    f = lambda v: torch.tensor(v, device=DEV, dtype=torch.float32)  # noqa: E731
-    return (out[:, :xd] * f(std) + f(mean)).contiguous()
-
-
 def test_shards_and_single_rows_are_bitwise_the_whole_run(dmip, golden):
     """Rows 500..800 alone (chain_offset = 500, 301 rows) equal those rows of a 1,000-row run; one row alone equals
     the same row among 37, for both entry points (quad / column cross-talk in the DPP broadcast or the output
