@@ -14,7 +14,8 @@ from .losses import (ConditionalScoreFPELoss, DSM_PDELoss, DSMLoss, PINNLoss, PI
                      ScoreFPELoss, batch_gradient, divergence)
 from .nets import MLP, MLP2, PosteriorScore
 from .problems import (LinearForwardProblem, ScatterometryEnergy, anneal_to_energy, energy_grad,
-                       generate_gt_samples, get_log_posterior, load_forward_model, mh_sample)
+                       generate_gt_samples, get_interpolated_energy_fun, get_log_posterior, langevin_step,
+                       load_forward_model, mala_sample, mh_sample)
 from .sdes import PluginReverseSDE, VariancePreservingSDE, sample_vp_truncated_q
 
 __all__ = [
@@ -23,7 +24,7 @@ __all__ = [
     "ScoreFPELoss", "batch_gradient", "divergence", "MLP", "MLP2", "PosteriorScore",
     "PluginReverseSDE", "VariancePreservingSDE", "sample_vp_truncated_q", "LinearForwardProblem",
     "ScatterometryEnergy", "anneal_to_energy", "energy_grad", "generate_gt_samples", "get_log_posterior",
-    "load_forward_model", "mh_sample",
+    "load_forward_model", "mh_sample", "mala_sample", "langevin_step", "get_interpolated_energy_fun",
 ]
 
 

@@ -43,7 +43,7 @@ EXPORTED = (
     "dmip_dps_sample_ex", "dmip_mh_sample_ex", "dmip_em_sample_lmbd", "dmip_flow_logp", "dmip_flow_logp_supported",
     "dmip_ode_sample", "dmip_ode_sample_supported", "dmip_flow_sample", "dmip_flow_sample_supported",
     "dmip_flow_logp_ex", "dmip_flow_sample_ex", "dmip_flow_logp_supported_precision",
-    "dmip_flow_sample_supported_precision",
+    "dmip_flow_sample_supported_precision", "dmip_mala_sample",
 )
 DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
 SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
@@ -186,6 +186,10 @@ def _declare(lib):
         lib.dmip_mh_sample_ex.argtypes = [_c_void_p, ctypes.POINTER(DmipScatNoise), _c_void_p, _i32, _i64, _i64, _i32,
                                           _f32, _u64t, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                                           _c_void_p]
+    if hasattr(lib, "dmip_mala_sample"):  # additive within ABI 9
+        lib.dmip_mala_sample.argtypes = [_c_void_p, ctypes.POINTER(DmipScatNoise), _c_void_p, _i32, _i64, _i64, _i32,
+                                         _i32, ctypes.c_double, ctypes.c_double, _u64t, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
     for name in EXPORTED:  # every entry point returns int but dmip_last_error
         if name != "dmip_last_error" and hasattr(lib, name):
             getattr(lib, name).restype = _i32
@@ -591,6 +595,17 @@ def mh_sample(handle, noise, y, n_chains, chain_offset, num_steps, noise_std, se
                                   int(chain_offset), int(num_steps), float(noise_std), _u64(seed), ptr(x_init),
                                   ptr(inj_noise), ptr(inj_unif), precision_code(precision), ptr(x_out), ptr(e_out),
                                   stream_of(y.device)))
+
+
+def mala_sample(handle, noise, y, n_chains, chain_offset, num_steps, lang_steps, stepsize, lambd, seed, x_out,
+                x_init=None, inj_eta=None, inj_unif=None, e_out=None, acc_out=None):
+    """dmip_mala_sample: fused Metropolis-adjusted Langevin chains (csrc/dmip_surrogate.hip mala_kernel), exact f32."""
+    calls["mala_sample"] += 1
+    _status_pending.add(_dev_index(y.device))
+    check(lib().dmip_mala_sample(handle.h, ctypes.byref(noise), ptr(y), int(y.shape[0]), int(n_chains),
+                                 int(chain_offset), int(num_steps), int(lang_steps), float(stepsize), float(lambd),
+                                 _u64(seed), ptr(x_init), ptr(inj_eta), ptr(inj_unif), ptr(x_out), ptr(e_out),
+                                 ptr(acc_out), stream_of(y.device)))
 
 
 def dps_sample(prior, surrogate, noise, sde, y, n_chains, chain_offset, num_steps, mean, std, seed, mode, zeta, out,

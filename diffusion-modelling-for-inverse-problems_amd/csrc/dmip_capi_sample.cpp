@@ -833,6 +833,41 @@ int dmip_mh_sample_ex(const dmip_surrogate* s, const dmip_scat_noise* noise, con
   return e == hipSuccess ? DMIP_OK : hip_fail(e, "mh_sample (fp32x3) launch");
 }
 
+int dmip_mala_sample(const dmip_surrogate* s, const dmip_scat_noise* noise, const float* y_dev, int n_y,
+                     int64_t n_chains, int64_t chain_offset, int num_steps, int lang_steps, double stepsize,
+                     double lambd, uint64_t seed, const float* x_init_dev, const float* eta_dev,
+                     const float* unif_dev, float* x_out_dev, float* e_out_dev, int32_t* acc_out_dev, void* stream) {
+  dmip::MalaParams q{};
+  if (int rc = mh_check(s, noise, q.s, y_dev, x_out_dev, n_y, n_chains, chain_offset, num_steps, 0.0f)) return rc;
+  if (lang_steps < 1) return fail(DMIP_ERR_INVALID, "lang_steps must be >= 1");
+  if (!std::isfinite(stepsize) || !(stepsize > 0.0) || !((float)stepsize > 0.0f) || !std::isfinite((float)stepsize))
+    return fail(DMIP_ERR_INVALID, "stepsize must be finite and > 0");
+  if (!(lambd >= 0.0 && lambd <= 1.0)) return fail(DMIP_ERR_INVALID, "lambd must be in [0, 1]");
+  if ((eta_dev == nullptr) != (unif_dev == nullptr))
+    return fail(DMIP_ERR_INVALID, "inject both the Langevin normals and the uniforms, or neither");
+  if (n_chains == 0) return DMIP_OK;
+  surrogate_params(s, q.s);
+  q.s.y = y_dev;
+  q.s.n_chains = n_chains;
+  q.s.chain_offset = chain_offset;
+  q.s.num_steps = num_steps;
+  q.s.seed = seed;
+  q.s.x_init = x_init_dev;
+  q.s.noise = eta_dev;
+  q.s.unif = unif_dev;
+  q.s.x_out = x_out_dev;
+  q.s.e_out = e_out_dev;
+  q.lang_steps = lang_steps;
+  // python scalars of the reference (models/SNF.py:294-297): each constant rounded once from double
+  q.h = (float)stepsize;
+  q.c = (float)std::sqrt(2.0 * stepsize);
+  q.lam_e = (float)lambd;
+  q.lam_q = (float)((1.0 - lambd) * 0.5);
+  q.acc_out = acc_out_dev;
+  hipError_t e = dmip::launch_mala(q, n_y, (hipStream_t)stream);
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "mala_sample launch");
+}
+
 // (the two DPS entry points refuse a bad guidance mode and a SiLU prior in opposite orders, so only what follows
 // their handle checks is shared: dps_check_sizes)
 int dmip_dps_sample(const dmip_mlp* prior, const dmip_surrogate* fwd, const dmip_scat_noise* noise,

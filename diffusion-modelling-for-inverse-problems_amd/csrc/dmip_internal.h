@@ -243,6 +243,17 @@ hipError_t launch_surrogate_eval(const SurrogateParams& p, int mode, int n_wg, h
 int surrogate_rows_per_wg();
 hipError_t launch_mh(const SurrogateParams& p, int n_y, hipStream_t st);
 
+// Metropolis-adjusted Langevin (dmip_surrogate.hip mala_kernel): the MH fields of `s` (s.noise / s.unif the injected
+// eta [S][L][n_y][n_chains][3] / u [S][n_y][n_chains]; s.noise_std unused) plus the Langevin proposal's constants
+struct MalaParams {
+  SurrogateParams s;
+  int lang_steps;      // L Langevin sub-steps per Metropolis step
+  float h, c;          // stepsize and sqrt(2 stepsize), each rounded once from double
+  float lam_e, lam_q;  // E_l = lam_e E + lam_q |x|^2: lambd and (1 - lambd) / 2
+  int* acc_out;        // [n_y][n_chains] accepted steps, or null
+};
+hipError_t launch_mala(const MalaParams& p, int n_y, hipStream_t st);
+
 // Exact-f32 networks (dmip_f32.hip, DMIP_PREC_F32): images packed by dmip_capi.cpp pack_f32_net.
 struct F32Net {
   const float* l1;     // [W/16 tiles][K1Q][64]: layer 1 over every input column, then the bias column

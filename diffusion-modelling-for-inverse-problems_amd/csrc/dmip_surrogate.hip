@@ -454,6 +454,125 @@ __global__ void __launch_bounds__(NW * 64, 1) mh_kernel(SurrogateParams p) {
   }
 }
 
+// ------------------------------------------------------- Metropolis-adjusted Langevin kernel
+// anneal_to_energy with langevin_prop=True (models/SNF.py:250-300) on the interpolated energy of
+// get_interpolated_energy_fun (models/SNF.py:220-231):
+//   E_l(x) = l E(x) + (1 - l) |x|^2 / 2,   grad E_l(x) = l grad E(x) + (1 - l) x
+// with E the negative log posterior above; l = 1 is E itself and l = 0 the Gaussian alone (the reference's
+// branches, taken by select so that a non-finite other term cannot leak in through a zero weight).
+// One evaluation = one forward and one reverse pass = one cycle of the ring (NCF + NCB chunks).
+template <typename E>
+__device__ __forceinline__ float interp_energy_grad(E& eng, const float* ylds, const MalaParams& q,
+                                                    const float (&x)[XD], float (&gr)[XD]) {
+  const SurrogateParams& p = q.s;
+  f32x4 f[2], v[2];
+  uint32_t m[3][2];
+  eng.forward(x, f, m);
+  const float e = energy(f, ylds, x, p.a, p.b2, p.lam, eng.g, v, true);
+  float gx[XD];
+  eng.backward(v, m, gx);
+  const float sq = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+  const bool one = q.lam_e == 1.0f, zero = q.lam_e == 0.0f;
+#pragma unroll
+  for (int d = 0; d < XD; ++d) {
+    const float ge = gx[d] + boundary_grad(x[d], p.lam);
+    gr[d] = one ? ge : (zero ? x[d] : q.lam_e * ge + (2.0f * q.lam_q) * x[d]);
+  }
+  return one ? e : (zero ? q.lam_q * sq : q.lam_e * e + q.lam_q * sq);
+}
+
+// Per Metropolis step: L Langevin sub-steps from (xx, gg) = (x, grad E_l(x)) with h = stepsize, c = sqrt(2 h):
+//   yy = xx - h gg + c eta;  eta' = (xx - yy + h grad E_l(yy)) / c;  ld += sum_d (eta_d^2 - eta'_d^2) / 2
+// then accept iff u < exp(-E_l(yy) + E_l(x) + ld). The chain state (x, E_l(x), grad E_l(x), RNG, accept count)
+// stays in registers for all steps; E_l and its gradient at the current point are carried (the reference
+// recomputes them: the same values), so a sub-step costs one evaluation. The state is chosen by select: a
+// non-finite proposal fails the comparison and is dropped, where the reference's blend rej * x + acc * x_prop
+// would turn 0 * inf into NaN. Outputs x, E_l(x_S) - E_l(x_0) and the number of accepted steps.
+// Product RNG per step: L x rng_normals<3>, then one word for u. INJECT: eta [S][L][n_y][n][3] and
+// u [S][n_y][n] replace it (replaying the reference's captured draws).
+template <bool INJECT>
+__global__ void __launch_bounds__(NW * 64, 1) mala_kernel(MalaParams q) {
+  const SurrogateParams& p = q.s;
+  __shared__ __attribute__((aligned(16))) char lds[RING_OFF_GRAD + R * CHUNK];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4;
+  const int yi = blockIdx.y;
+  const long long c_local = (long long)blockIdx.x * (NW * 16) + w * 16 + (lane & 15);
+  const bool valid = c_local < p.n_chains;
+  const long long cc = valid ? c_local : 0;
+  Engine<true, RING_OFF_GRAD, PlanGrad> eng{lds, make_plan<PlanGrad>(p), 0, w, lane, g};
+  float* ylds = (float*)(lds + Y_OFF);
+  for (int i = threadIdx.x; i < 32; i += NW * 64) ylds[i] = i < YD ? p.y[(size_t)yi * YD + i] : 0.0f;
+  eng.prologue(p);
+
+  Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
+  float x[XD];
+  if (p.x_init) {
+#pragma unroll
+    for (int d = 0; d < XD; ++d) x[d] = p.x_init[((size_t)yi * p.n_chains + cc) * XD + d];
+  } else {
+#pragma unroll
+    for (int d = 0; d < XD; ++d) x[d] = (float)(rng_next(rng) >> 8) * 0x1p-24f * 2.0f - 1.0f;
+  }
+  float g_cur[XD];
+  const float e0 = interp_energy_grad(eng, ylds, q, x, g_cur);
+  float e_cur = e0;
+  int n_acc = 0;
+  const size_t plane = (size_t)gridDim.y * p.n_chains;
+  const size_t at = (size_t)yi * p.n_chains + cc;
+  for (int s = 0; s < p.num_steps; ++s) {
+    float xx[XD], gg[XD], ld = 0.0f, e_y = e_cur;
+#pragma unroll
+    for (int d = 0; d < XD; ++d) xx[d] = x[d], gg[d] = g_cur[d];
+#pragma unroll 1
+    for (int l = 0; l < q.lang_steps; ++l) {
+      float eta[XD];
+      if constexpr (INJECT) {
+        const float* src = p.noise + (((size_t)s * q.lang_steps + l) * plane + at) * XD;
+#pragma unroll
+        for (int d = 0; d < XD; ++d) eta[d] = src[d];
+      } else {
+        rng_normals<XD>(rng, eta);
+      }
+      float yy[XD], g_y[XD];
+#pragma unroll
+      for (int d = 0; d < XD; ++d) yy[d] = xx[d] - q.h * gg[d] + q.c * eta[d];
+      e_y = interp_energy_grad(eng, ylds, q, yy, g_y);
+      float dsum = 0.0f;
+#pragma unroll
+      for (int d = 0; d < XD; ++d) {
+        const float eb = (xx[d] - yy[d] + q.h * g_y[d]) / q.c;
+        dsum += eta[d] * eta[d] - eb * eb;
+        xx[d] = yy[d];
+        gg[d] = g_y[d];
+      }
+      ld += 0.5f * dsum;
+      // the carried sums stay one dependent chain per sub-step
+      asm volatile("" : "+v"(ld), "+v"(e_y));
+    }
+    float u;
+    if constexpr (INJECT) u = p.unif[(size_t)s * plane + at];
+    else u = (float)(rng_next(rng) >> 8) * 0x1p-24f;
+    const bool acc = u < expf(-e_y + e_cur + ld);
+#pragma unroll
+    for (int d = 0; d < XD; ++d) {
+      x[d] = acc ? xx[d] : x[d];
+      g_cur[d] = acc ? gg[d] : g_cur[d];
+    }
+    e_cur = acc ? e_y : e_cur;
+    n_acc += acc ? 1 : 0;
+  }
+  eng.epilogue();
+  if (valid && g == 0) {
+    float* dst = p.x_out + at * XD;
+#pragma unroll
+    for (int d = 0; d < XD; ++d) dst[d] = x[d];
+    if (p.e_out) p.e_out[at] = e_cur - e0;
+    if (q.acc_out) q.acc_out[at] = n_acc;
+  }
+}
+
 
 // ---------------------------------------------------------------------------- DPS sampler
 // BASELINE config 4 (no reference code for sampling-time guidance): diffusion
@@ -698,6 +817,16 @@ hipError_t launch_mh(const SurrogateParams& p, int n_y, hipStream_t st) {
     hipLaunchKernelGGL(sg::mh_kernel<true>, grid, block, 0, st, p);
   else
     hipLaunchKernelGGL(sg::mh_kernel<false>, grid, block, 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_mala(const MalaParams& q, int n_y, hipStream_t st) {
+  const long long per_wg = sg::NW * 16;
+  const dim3 grid((unsigned)((q.s.n_chains + per_wg - 1) / per_wg), (unsigned)n_y), block(sg::NW * 64);
+  if (q.s.noise)
+    hipLaunchKernelGGL(sg::mala_kernel<true>, grid, block, 0, st, q);
+  else
+    hipLaunchKernelGGL(sg::mala_kernel<false>, grid, block, 0, st, q);
   return hipGetLastError();
 }
 

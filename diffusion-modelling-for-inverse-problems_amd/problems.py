@@ -4,8 +4,8 @@ working: linear_problem.py:5-65, utils_scatterometry.py:8-52, datasets.py:8-54, 
 
 The data producers are host-side torch ops; the hot path consumes their outputs (y observations,
 training pairs) on the device. The scatterometry posterior itself (get_log_posterior, energy_grad)
-and the Metropolis-Hastings ground-truth sampler (anneal_to_energy) run on the device as fused
-exact-f32 MFMA kernels (libdmip dmip_log_posterior / dmip_mh_sample, csrc/dmip_surrogate.hip)
+and the Metropolis-Hastings samplers (anneal_to_energy: random-walk and Langevin proposals) run on the device as fused
+exact-f32 MFMA kernels (libdmip dmip_log_posterior / dmip_mh_sample / dmip_mala_sample, csrc/dmip_surrogate.hip)
 whenever the samples are on a HIP device and the forward model is the reference's surrogate shape.
 """
 import os
@@ -191,14 +191,23 @@ def energy_grad(x, energy):
 # ------------------------------------------------------- Metropolis-Hastings ground truth (F3)
 class ScatterometryEnergy:
     """energy(x) = get_log_posterior(x, forward_model, a, b, y, lambd_bd) for one observation y -- the
-    `mcmc_energy` of generate_scatterometry_ground_truth.py:61 as an object anneal_to_energy can fuse."""
+    `mcmc_energy` of generate_scatterometry_ground_truth.py:61 as an object anneal_to_energy can fuse.
+    With lambd < 1 it is the interpolated energy of get_interpolated_energy_fun (models/SNF.py:220-231):
+    lambd E(x) + (1 - lambd) |x|^2 / 2, the intermediate densities the SNF's MCMC and Langevin layers anneal through."""
 
-    def __init__(self, forward_model, a, b, y, lambd_bd):
+    def __init__(self, forward_model, a, b, y, lambd_bd, lambd=1.0):
         self.forward_model, self.a, self.b, self.lambd_bd = forward_model, a, b, lambd_bd
         self.y = torch.as_tensor(y, dtype=torch.float32).reshape(-1)
+        self.lambd = float(lambd)
+        if not 0.0 <= self.lambd <= 1.0:
+            raise ValueError(f"ScatterometryEnergy: lambd {lambd!r} outside [0, 1]")
 
     def __call__(self, x):
-        return get_log_posterior(x, self.forward_model, self.a, self.b, self.y.to(x.device)[None, :], self.lambd_bd)
+        post = lambda v, ys: get_log_posterior(v, self.forward_model, self.a, self.b, ys, self.lambd_bd)
+        return get_interpolated_energy_fun(self.y.to(x.device)[None, :], self.lambd, post)(x)
+
+    def params(self):
+        return {'a': self.a, 'b': self.b, 'lambd_bd': self.lambd_bd}
 
 
 def mh_sample(forward_model, params, ys, n_chains, num_steps, noise_std, seed=None, chain_offset=0, x_init=None,
@@ -248,49 +257,144 @@ def mh_sample(forward_model, params, ys, n_chains, num_steps, noise_std, seed=No
     return parallel.guarded(dev, run(precision), run("fp32") if precision == "fp32x3" else None, agree)
 
 
+def mala_sample(forward_model, params, ys, n_chains, num_steps, stepsize, lang_steps=1, lambd=1.0, seed=None,
+                chain_offset=0, x_init=None, eta=None, unif=None, return_ediff=False, return_accept=False, agree=None):
+    """Fused Metropolis-adjusted Langevin chains (dmip_mala_sample) for every row of ys (n_y, 23): device tensor
+    (n_y, n_chains, 3). Each of the num_steps Metropolis steps proposes by lang_steps Langevin sub-steps of size
+    stepsize on E_lambd = lambd E + (1 - lambd) |x|^2 / 2 (E = get_log_posterior(., y); anneal_to_energy with
+    langevin_prop=True, models/SNF.py:250-300). x_init (n_y, n_chains, 3) or None for x0 ~ U[-1, 1]^3 from the chain
+    RNG; eta (S, lang_steps, n_y, n_chains, 3) / unif (S, n_y, n_chains) replay captured draws. return_ediff adds
+    E_lambd(x_S) - E_lambd(x_0) (n_y, n_chains), return_accept the int32 count of accepted steps per chain. Exact f32
+    only; any failure is collective under `agree` (parallel.guarded, no fallback)."""
+    from . import _lib, parallel
+    ys = torch.as_tensor(ys)
+    if not torch.cuda.is_available():
+        raise RuntimeError("dmip: MALA sampling needs a HIP device (fused kernel; there is no CPU path)")
+    dev = ys.device if ys.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    ys = ys.to(device=dev, dtype=torch.float32).reshape(-1, 23).contiguous()
+    h = surrogate_handle(forward_model, dev)
+    if h is None:
+        raise ValueError("mala_sample: forward_model is not the scatterometry surrogate shape (3 -> 256^3 -> 23)")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    n_y, n, S, L = ys.shape[0], int(n_chains), int(num_steps), int(lang_steps)
+    prep = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
+    x0, eta, unif = prep(x_init), prep(eta), prep(unif)
+    for name, t, shape in (("x_init", x0, (n_y, n, 3)), ("eta", eta, (S, L, n_y, n, 3)), ("unif", unif, (S, n_y, n))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"mala_sample: {name} has shape {tuple(t.shape)}, expected {shape}")
+    out = torch.empty(n_y, n, 3, device=dev, dtype=torch.float32)
+    ed = torch.empty(n_y, n, device=dev, dtype=torch.float32) if return_ediff else None
+    na = torch.empty(n_y, n, device=dev, dtype=torch.int32) if return_accept else None
+    nz = _lib.scat_noise(params['a'], params['b'], params['lambd_bd'])
+
+    def launch():
+        _lib.mala_sample(h, nz, ys, n, chain_offset, S, L, stepsize, lambd, seed, out, x0, eta, unif, ed, na)
+        res = (out,) + ((ed,) if return_ediff else ()) + ((na,) if return_accept else ())
+        return res if len(res) > 1 else out
+
+    return parallel.guarded(dev, launch, None, agree)
+
+
+def get_interpolated_energy_fun(ys, lambd, get_log_posterior):
+    """models/SNF.py:220-231: the energy lambd * get_log_posterior(x, ys) + (1 - lambd) |x|^2 / 2 between the standard
+    normal (lambd == 0) and the posterior (lambd == 1); those two ends are branches of their own, as in the reference."""
+    if lambd == 0.:
+        def energy(x):
+            return 0.5 * torch.sum(x ** 2, dim=1)
+        return energy
+    if lambd == 1.:
+        def energy(x):
+            return get_log_posterior(x, ys)
+        return energy
+
+    def energy(x):
+        return lambd * (get_log_posterior(x, ys)).view(len(x)) + (1 - lambd) * 0.5 * torch.sum(x ** 2, dim=1)
+    return energy
+
+
+def langevin_step(x, stepsize, energy, lang_steps):
+    """models/SNF.py:286-300: lang_steps unadjusted Langevin steps y = x - h grad E(x) + sqrt(2 h) eta. Returns
+    (x_L, log_det, E(x_0), E(x_L)) with log_det = sum over the steps of (|eta|^2 - |eta'|^2) / 2, eta' the noise of the
+    reverse move -- the log proposal ratio anneal_to_energy adds to its acceptance exponent."""
+    log_det = torch.zeros((x.shape[0], 1), device=x.device)
+    beta = 1.
+    for i in range(lang_steps):
+        eta = torch.randn_like(x)
+        grad_x, e_x = energy_grad(x, energy)
+        if i == 0:
+            energy_x = e_x
+        y = x - stepsize * grad_x + np.sqrt(2 * stepsize / beta) * eta
+        grad_y, energy_y = energy_grad(y, energy)
+        eta_ = (x - y + stepsize * grad_y) / np.sqrt(2 * stepsize / beta)
+        log_det = log_det + 0.5 * (eta ** 2 - eta_ ** 2).sum(axis=1, keepdims=True)
+        x = y
+    return x, log_det.view(len(x)), energy_x, energy_y
+
+
 def anneal_to_energy(x_curr, energy, metr_steps_per_block, noise_std=0.1, langevin_prop=False, lang_steps=None,
                      stepsize=None):
-    """models/SNF.py:250-275 (random-walk proposals). Returns (x, E(x) - E(x0)). With a
-    ScatterometryEnergy and device samples: one fused launch for all steps; any other energy
-    callable: the reference's loop (its energy evaluations still go to the device kernel when the
-    callable is get_log_posterior on device samples)."""
-    if langevin_prop:
-        raise NotImplementedError("Langevin proposals belong to the SNF baseline (out of scope, SURVEY.md §2)")
-    if isinstance(energy, ScatterometryEnergy) and x_curr.is_cuda:
+    """models/SNF.py:250-275. Returns (x, E(x) - E(x0)). Random-walk proposals x + noise_std xi, or with
+    langevin_prop=True Metropolis-adjusted Langevin proposals (langevin_step: lang_steps sub-steps of size stepsize).
+    With a ScatterometryEnergy and device samples: one fused launch for all steps (mh_sample, at lambd == 1, or
+    mala_sample); any other energy callable, on any device: the reference's loop in torch (its energy evaluations
+    still go to the device kernel when the callable is get_log_posterior on device samples)."""
+    if langevin_prop and (lang_steps is None or stepsize is None):
+        raise ValueError("anneal_to_energy: langevin_prop=True needs lang_steps and stepsize")
+    fused = isinstance(energy, ScatterometryEnergy) and x_curr.is_cuda
+    if fused and (langevin_prop or energy.lambd == 1.0):
         x0 = x_curr.detach().to(torch.float32).reshape(1, -1, 3).contiguous()
-        x, ed = mh_sample(energy.forward_model, {'a': energy.a, 'b': energy.b, 'lambd_bd': energy.lambd_bd},
-                          energy.y.to(x_curr.device)[None, :], x0.shape[1], metr_steps_per_block, noise_std,
-                          x_init=x0, return_ediff=True)
+        y = energy.y.to(x_curr.device)[None, :]
+        if langevin_prop:
+            x, ed = mala_sample(energy.forward_model, energy.params(), y, x0.shape[1], metr_steps_per_block, stepsize,
+                                lang_steps=lang_steps, lambd=energy.lambd, x_init=x0, return_ediff=True)
+        else:
+            x, ed = mh_sample(energy.forward_model, energy.params(), y, x0.shape[1], metr_steps_per_block, noise_std,
+                              x_init=x0, return_ediff=True)
         return x[0], ed[0]
     e0 = energy(x_curr)
     e_curr = e0
     for _ in range(metr_steps_per_block):
-        x_prop = x_curr + noise_std * torch.randn_like(x_curr)
-        e_prop = energy(x_prop)
-        e_curr = energy(x_curr)
-        acc = (torch.rand_like(e_prop) < torch.exp(-e_prop + e_curr)).float().view(len(x_prop), 1)
+        if langevin_prop:
+            x_prop, log_det, e_curr, e_prop = langevin_step(x_curr, stepsize, energy, lang_steps)
+            e_diff = torch.exp(-e_prop + e_curr + log_det)
+        else:
+            x_prop = x_curr + noise_std * torch.randn_like(x_curr)
+            e_prop = energy(x_prop)
+            e_curr = energy(x_curr)
+            e_diff = torch.exp(-e_prop + e_curr)
+        acc = (torch.rand_like(e_diff) < e_diff).float().view(len(x_prop), 1)
         x_curr = (1. - acc) * x_curr + acc * x_prop
         e_curr = (1. - acc.view(-1)) * e_curr + acc.view(-1) * e_prop
     return x_curr, e_curr.view(-1) - e0.view(-1)
 
 
 def generate_gt_samples(forward_model, params, ys, out_dir=None, n_samples_x=30000, n_repeats=10, metr_steps=1000,
-                        noise_std=0.5, seed=None, precision="fp32"):
+                        noise_std=0.5, seed=None, precision="fp32", langevin_prop=False, lang_steps=1, stepsize=None):
     """generate_scatterometry_ground_truth.py:26-63 on the device: for every y and repeat j,
     n_samples_x MH chains from U[-1, 1]^3 for metr_steps steps (NOISE_STD_MCMC, METR_STEPS of
     config_scatterometry.yml), all in one launch (precision as mh_sample); under torch.distributed the chains
     are sharded over the ranks (parallel.chains_sharded: every rank gets the whole, bit-identical to one GPU; rank 0
-    writes the files); optionally written as out_dir/<i>/<j>.npy. Returns a device tensor (n_y, n_repeats, n_samples_x, 3)."""
+    writes the files); optionally written as out_dir/<i>/<j>.npy. Returns a device tensor (n_y, n_repeats, n_samples_x, 3).
+    langevin_prop=True runs the same chains with Langevin proposals (mala_sample: lang_steps, stepsize; exact f32)."""
     from . import parallel
     ys = torch.as_tensor(ys, dtype=torch.float32).reshape(-1, 23)
     rows = ys.repeat_interleave(n_repeats, dim=0)
     if not torch.cuda.is_available():
         raise RuntimeError("dmip: MH sampling needs a HIP device (fused kernel; there is no CPU path)")
+    if langevin_prop and stepsize is None:
+        raise ValueError("generate_gt_samples: langevin_prop=True needs a stepsize")
+    if langevin_prop and precision != "fp32":
+        raise ValueError("generate_gt_samples: Langevin proposals run in exact f32 (precision=\"fp32\")")
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     dev = ys.device if ys.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    run = lambda n, off, s, agree: mh_sample(forward_model, params, rows, n, metr_steps, noise_std, seed=s,
-                                             chain_offset=off, precision=precision, agree=agree)
+    if langevin_prop:
+        run = lambda n, off, s, agree: mala_sample(forward_model, params, rows, n, metr_steps, stepsize,
+                                                   lang_steps=lang_steps, seed=s, chain_offset=off, agree=agree)
+    else:
+        run = lambda n, off, s, agree: mh_sample(forward_model, params, rows, n, metr_steps, noise_std, seed=s,
+                                                 chain_offset=off, precision=precision, agree=agree)
     x = parallel.chains_sharded(n_samples_x, run, seed, dev)  # one process: a single launch of all chains
     x = x.reshape(ys.shape[0], n_repeats, n_samples_x, 3)
     rank, ws = parallel.world()

@@ -437,6 +437,25 @@ int dmip_mh_sample_ex(const dmip_surrogate* s, const dmip_scat_noise* noise, con
                       const float* x_init_dev, const float* noise_dev, const float* unif_dev, int precision,
                       float* x_out_dev, float* e_out_dev, void* stream);
 
+/* Metropolis-adjusted Langevin sampler (MALA), fused like dmip_mh_sample (additive entry point; the ABI version
+ * stays 9). Replaces: anneal_to_energy(x0, energy, num_steps, langevin_prop=True, lang_steps, stepsize)
+ * (models/SNF.py:250-300) with energy = get_interpolated_energy_fun(y, lambd, get_log_posterior)
+ * (models/SNF.py:220-231): E_l(x) = lambd E(x) + (1 - lambd) |x|^2 / 2, E = get_log_posterior(., y). Per step,
+ * from (xx, gg) = (x, grad E_l(x)), with h = stepsize and c = (float)sqrt(2 h), lang_steps times:
+ *   yy = xx - h gg + c eta;  eta' = (xx - yy + h grad E_l(yy)) / c;  ld += sum_d (eta_d^2 - eta'_d^2) / 2;  xx = yy
+ * then accept x = xx iff u < exp(-E_l(xx) + E_l(x) + ld); a non-finite proposal is rejected.
+ *   y_dev, x_init_dev, x_out_dev, e_out_dev, seed, chain_offset: as dmip_mh_sample (e_out = E_l(x_S) - E_l(x_0))
+ *   lang_steps >= 1;  stepsize finite and > 0;  0 <= lambd <= 1
+ *   eta_dev / unif_dev   NULL, or injected normals [S][lang_steps][n_y][n_chains][3] and acceptance uniforms
+ *               [S][n_y][n_chains] (replaying captured draws; both or neither)
+ *   acc_out_dev (optional) int32 [n_y][n_chains]: the number of accepted steps of each chain
+ * Product RNG per step and chain: lang_steps x 3 normals (two Box-Muller pairs each), then one word for u.
+ * Exact f32 arithmetic; one forward and one reverse pass of the surrogate per Langevin sub-step. */
+int dmip_mala_sample(const dmip_surrogate* s, const dmip_scat_noise* noise, const float* y_dev, int n_y,
+                     int64_t n_chains, int64_t chain_offset, int num_steps, int lang_steps, double stepsize,
+                     double lambd, uint64_t seed, const float* x_init_dev, const float* eta_dev,
+                     const float* unif_dev, float* x_out_dev, float* e_out_dev, int32_t* acc_out_dev, void* stream);
+
 /* Diffusion posterior sampling (DPS, Chung et al. 2023) on the reference's Euler-Maruyama predictor:
  * BASELINE config 4. The reference has no sampling-time guidance (its "Posterior"
  * estimator learns the likelihood score with PosteriorLoss, losses.py:293-386); this is the build's
