@@ -29,7 +29,7 @@ $(CSRC)/dmip_train.o: $(CSRC)/dmip_train.hip $(HDRS)
 $(CSRC)/dmip_eval.o: $(CSRC)/dmip_eval.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/dmip_surrogate.o: $(CSRC)/dmip_surrogate.hip $(HDRS)
+$(CSRC)/dmip_surrogate.o: $(CSRC)/dmip_surrogate.hip $(CSRC)/dmip_mh_chains.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/dmip_gemm.o: $(CSRC)/dmip_gemm.hip $(HDRS)
@@ -77,7 +77,7 @@ $(CSRC)/dmip_x3k.o: $(CSRC)/dmip_x3k.hip $(CSRC)/dmip_x3k.h $(CSRC)/dmip_x3.h $(
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 # DPS (config 4) on the split-fp16 arithmetic
-$(CSRC)/dmip_dps_x3.o: $(CSRC)/dmip_dps_x3.hip $(CSRC)/dmip_x3.h $(HDRS)
+$(CSRC)/dmip_dps_x3.o: $(CSRC)/dmip_dps_x3.hip $(CSRC)/dmip_mh_chains.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/dmip_capi_%.o: $(CSRC)/dmip_capi_%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)

@@ -732,6 +732,12 @@ int dps_check_sizes(int n_y, int64_t n_chains, int64_t chain_offset, int num_ste
   return DMIP_OK;
 }
 
+// the chains of an MH, MALA or DPS launch over the surrogate, whatever kernel runs them (DPS: no start states)
+dmip::MhChains fill_chains(int64_t n_chains, int64_t chain_offset, int num_steps, float noise_std, uint64_t seed,
+                           const float* x_init_dev, const float* noise_dev, const float* unif_dev, float* x_out_dev) {
+  return dmip::MhChains{n_chains, chain_offset, num_steps, noise_std, seed, x_init_dev, noise_dev, unif_dev, x_out_dev};
+}
+
 int dps_prior_refused() {
   return fail(DMIP_ERR_UNSUPPORTED, "DPS prior must be an x,t network (MLP2) with xdim 3 and hidden layers [256]*3");
 }
@@ -783,15 +789,7 @@ int dmip_mh_sample(const dmip_surrogate* s, const dmip_scat_noise* noise, const 
   if (n_chains == 0) return DMIP_OK;
   surrogate_params(s, p);
   p.y = y_dev;
-  p.n_chains = n_chains;
-  p.chain_offset = chain_offset;
-  p.num_steps = num_steps;
-  p.noise_std = noise_std;
-  p.seed = seed;
-  p.x_init = x_init_dev;
-  p.noise = noise_dev;
-  p.unif = unif_dev;
-  p.x_out = x_out_dev;
+  p.ch = fill_chains(n_chains, chain_offset, num_steps, noise_std, seed, x_init_dev, noise_dev, unif_dev, x_out_dev);
   p.e_out = e_out_dev;
   hipError_t e = dmip::launch_mh(p, n_y, (hipStream_t)stream);
   return e == hipSuccess ? DMIP_OK : hip_fail(e, "mh_sample launch");
@@ -816,16 +814,11 @@ int dmip_mh_sample_ex(const dmip_surrogate* s, const dmip_scat_noise* noise, con
   p.sl1 = s->x3_l1;
   p.sbias = s->x3_bias;
   p.y = y_dev;
-  p.n_chains = n_chains;
-  p.chain_offset = chain_offset;
-  p.num_steps = num_steps;
-  p.noise_std = noise_std;
+  p.ch = fill_chains(n_chains, chain_offset, num_steps, noise_std, seed, x_init_dev, /*noise_dev=*/nullptr,
+                     /*unif_dev=*/nullptr, x_out_dev);
   p.a = sp.a;
   p.b2 = sp.b2;
   p.lam = sp.lam;
-  p.seed = seed;
-  p.x_init = x_init_dev;
-  p.x_out = x_out_dev;
   p.e_out = e_out_dev;
   p.err = status_word(dmip::stream_device(st));
   if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
@@ -848,14 +841,8 @@ int dmip_mala_sample(const dmip_surrogate* s, const dmip_scat_noise* noise, cons
   if (n_chains == 0) return DMIP_OK;
   surrogate_params(s, q.s);
   q.s.y = y_dev;
-  q.s.n_chains = n_chains;
-  q.s.chain_offset = chain_offset;
-  q.s.num_steps = num_steps;
-  q.s.seed = seed;
-  q.s.x_init = x_init_dev;
-  q.s.noise = eta_dev;
-  q.s.unif = unif_dev;
-  q.s.x_out = x_out_dev;
+  q.s.ch = fill_chains(n_chains, chain_offset, num_steps, /*noise_std=*/0.0f, seed, x_init_dev, /*noise_dev=*/eta_dev,
+                       unif_dev, x_out_dev);
   q.s.e_out = e_out_dev;
   q.lang_steps = lang_steps;
   // python scalars of the reference (models/SNF.py:294-297): each constant rounded once from double
@@ -887,11 +874,8 @@ int dmip_dps_sample(const dmip_mlp* prior, const dmip_surrogate* fwd, const dmip
   surrogate_params(fwd, p.s);
   p.mode = mode;
   p.s.y = y_dev;
-  p.s.n_chains = n_chains;
-  p.s.chain_offset = chain_offset;
-  p.s.num_steps = num_steps;
-  p.s.seed = seed;
-  p.s.x_out = x_out_dev;
+  p.s.ch = fill_chains(n_chains, chain_offset, num_steps, /*noise_std=*/0.0f, seed, /*x_init_dev=*/nullptr,
+                       /*noise_dev=*/nullptr, /*unif_dev=*/nullptr, x_out_dev);
   p.pl1 = prior->dps_l1;
   p.pw2 = prior->dps_w2;
   p.pw3 = prior->dps_w3;

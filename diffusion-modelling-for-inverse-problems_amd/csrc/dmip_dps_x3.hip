@@ -23,10 +23,10 @@
 // The reverse passes carry a per-chain power-of-two scale (exact) so the split operands stay inside fp16's range;
 // a surrogate activation or an input beyond it is reported (kErrRange, dmip_device_status), as the fp32x3 samplers
 // do, and the Python default resamples in exact f32.
+#include "dmip_mh_chains.h"
 #include "dmip_x3.h"
 
 #include <cstdlib>
-#include <utility>
 
 namespace dmip {
 namespace dx3 {
@@ -689,35 +689,7 @@ __global__ void __launch_bounds__(NW * 64, 1) dps_x3_kernel(DpsX3Params p) {
 // forward half of the DPS kernel's surrogate pass (layer 1 resident, S2 | S3 | Sout streamed, 17 chunks per step,
 // the mid-chunk ring protocol). Same RNG consumption per chain (x0 ~ U[-1, 1]^3 unless given, then per step 3
 // proposal normals and one acceptance uniform), same energy function and acceptance test; four waves of 16 chains.
-
-// get_log_posterior's energy of one chain (dmip_surrogate.hip energy, the same operations): 0.5 sum log pref +
-// 0.5 sum (y - f)^2 / pref + lam sum of the box violations, pref = (a f)^2 + b^2
-__device__ __forceinline__ float mh_energy(const f32x4 (&f)[2], const float* y, const float (&x)[3], float a,
-                                           float b2, float lam, int g) {
-  float slog = 0.0f, ssq = 0.0f;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * t + 4 * g + r;
-      if (row < kSurYdim) {
-        const float fk = f[t][r];
-        const float af = a * fk;
-        const float pref = af * af + b2;
-        const float res = y[row] - fk;
-        slog += logf(pref);
-        ssq += res * res / pref;
-      }
-    }
-  slog += __shfl_xor(slog, 16, 64);
-  slog += __shfl_xor(slog, 32, 64);
-  ssq += __shfl_xor(ssq, 16, 64);
-  ssq += __shfl_xor(ssq, 32, 64);
-  float bd = 0.0f;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) bd += fmaxf(x[d] - 1.0f, 0.0f) + fmaxf(-1.0f - x[d], 0.0f);
-  return 0.5f * slog + 0.5f * ssq + lam * bd;
-}
+// The chain life cycle, the energy and the step loop are dmip_mh_chains.h's; a kernel here is its forward engine.
 
 // the surrogate's forward pass at x (every lane of the chain holds x): output rows f (tiles 0, 1), range flag
 __device__ __forceinline__ void sur_forward(Eng& e, const float (&x)[3], int g, int& vmax, f32x4 (&f)[2]) {
@@ -744,15 +716,6 @@ __device__ __forceinline__ void sur_forward(Eng& e, const float (&x)[3], int g, 
 // where the m-major order (input and output operands live together, 128 registers a tile) does not. The chunk's
 // LDS reads and its share of the refill (the guide's 60-185 issue cycles per 1 KiB piece) are spread over MT times
 // the matrix work. Same ring and mid-chunk barrier protocol as mid_units; the output layer's chunk stays m-major.
-// compile-time loops over the tiles (the index is a constant in every body)
-template <typename F, int... I>
-__device__ __forceinline__ void sfor_impl(const F& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void sfor(const F& f) {
-  sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
 struct EngK {
   char* lds;
   const char* img;  // the surrogate's DPS image: S2 | S3 (8 m-major chunks each) | Sout | ...
@@ -967,155 +930,82 @@ __device__ __forceinline__ void sur_forward_mt(EngK& e, const float (&x)[MT][3],
   chunk_k<MT, true, 0, 2>(e, P, f, Hh, Hl, vmax);
 }
 
+// the resident parts of an MH workgroup: the surrogate's layer-1 image (lanes 0-31 of each tile), its biases, y
+__device__ __forceinline__ void stage_surrogate(char* lds, const MhX3Params& p, int yi) {
+  const uint4* s2 = (const uint4*)p.sl1;
+  uint4* d2 = (uint4*)(lds + SL1);
+  for (int i = threadIdx.x; i < ST * 32; i += NW * 64) d2[i] = s2[(i >> 5) * 64 + (i & 31)];
+  float* sb = (float*)(lds + SB);
+  for (int i = threadIdx.x; i < 3 * W + 32; i += NW * 64) sb[i] = p.sbias[i];
+  stage_y<NW>((float*)(lds + YO), p.y, yi);
+  __syncthreads();
+}
+
+// one tile per wave on the DPS kernel's m-major engine (the A/B knob DMIP_MH_MT=1, never the product path)
 __global__ void __launch_bounds__(NW * 64, 1) mh_x3_kernel(MhX3Params p) {
   __shared__ __attribute__((aligned(16))) char lds[TOTAL];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = lane >> 4, j = lane & 15;
+  const int g = lane >> 4;
   const int yi = blockIdx.y;
-  const long long c_local = (long long)blockIdx.x * (NW * 16) + w * 16 + j;
-  const bool valid = c_local < p.n_chains;
-  const long long cc = valid ? c_local : 0;
+  const ChainLane ln[1] = {chain_lane<NW>(w, lane, p.ch.n_chains, yi)};
   Eng e{lds, p.simg, 0, 0, 0, w, lane, g};
   e.nstream = kDpsX3SurFwdChunks;
   e.init_dma();
-  {
-    const uint4* s2 = (const uint4*)p.sl1;
-    uint4* d2 = (uint4*)(lds + SL1);
-    for (int i = threadIdx.x; i < ST * 32; i += NW * 64) d2[i] = s2[(i >> 5) * 64 + (i & 31)];
-    float* sb = (float*)(lds + SB);
-    for (int i = threadIdx.x; i < 3 * W + 32; i += NW * 64) sb[i] = p.sbias[i];
-    float* yo = (float*)(lds + YO);
-    for (int i = threadIdx.x; i < 32; i += NW * 64) yo[i] = i < kSurYdim ? p.y[(size_t)yi * kSurYdim + i] : 0.0f;
-    __syncthreads();
-    e.start_mid();
-  }
+  stage_surrogate(lds, p, yi);
+  e.start_mid();
   const float* ylds = (const float*)(lds + YO);
-  Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
-  float x[3];
-  if (p.x_init) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) x[d] = p.x_init[((size_t)yi * p.n_chains + cc) * 3 + d];
-  } else {  // torch.rand(n, 3) * 2 - 1 (generate_scatterometry_ground_truth.py:27)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) x[d] = (float)(rng_next(rng) >> 8) * 0x1p-24f * 2.0f - 1.0f;
-  }
+  float x[1][3], de[1];
+  Rng rng[1] = {chain_start(p.ch, ln[0], x[0])};
   bool oor = false;
   int vmax = 0;  // track4's running max of the split values (float bits)
-  for (int d = 0; d < 3; ++d) oor |= beyond_fp16(x[d]);
-  f32x4 f[2];
-  sur_forward(e, x, g, vmax, f);
-  const float e0 = mh_energy(f, ylds, x, p.a, p.b2, p.lam, g);
-  float e_cur = e0;
-  for (int s = 0; s < p.num_steps; ++s) {
-    float xi[3];
-    rng_normals<3>(rng, xi);
-    const float u = (float)(rng_next(rng) >> 8) * 0x1p-24f;
-    float xp[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      xp[d] = x[d] + p.noise_std * xi[d];
-      oor |= beyond_fp16(xp[d]);
-    }
-    sur_forward(e, xp, g, vmax, f);
-    const float e_prop = mh_energy(f, ylds, xp, p.a, p.b2, p.lam, g);
-    const bool acc = u < expf(-e_prop + e_cur);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) x[d] = acc ? xp[d] : x[d];
-    e_cur = acc ? e_prop : e_cur;
-  }
+  const auto eval = [&](const float (&xs)[1][3], float (&es)[1]) __attribute__((always_inline)) {
+    for (int d = 0; d < 3; ++d) oor |= beyond_fp16(xs[0][d]);
+    f32x4 f[2];
+    sur_forward(e, xs[0], g, vmax, f);
+    es[0] = scat_energy(f, ylds, xs[0], p.a, p.b2, p.lam, g);
+  };
+  random_walk<1, false>(p.ch, ln, rng, x, de, eval);
   wait_vmcnt<0>();  // the prefetched chunks of a step that never ran land before the workgroup exits
-  x3::report_range((oor || range_bad(vmax)) && valid, p.err, lane);
-  if (valid && g == 0) {
-    float* dst = p.x_out + ((size_t)yi * p.n_chains + c_local) * 3;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) dst[d] = x[d];
-    if (p.e_out) p.e_out[(size_t)yi * p.n_chains + c_local] = e_cur - e0;
-  }
+  x3::report_range((oor || range_bad(vmax)) && ln[0].valid, p.err, lane);
+  chain_store(p.ch, ln[0], g, x[0], p.e_out, de[0]);
 }
 
-// mh_x3_kernel on the k-major multi-tile engine: 16 MT chains per wave, tile m's chain j at 64 MT block + 16 (MT w + m)
-// + j; per chain the same RNG stream, proposals, energy and acceptance test as mh_x3_kernel
+// the k-major multi-tile engine: 16 MT chains per wave (chain_lane's tile m); per chain the same RNG stream, proposals,
+// energy and acceptance test as mh_x3_kernel
 template <int MT>
 __global__ void __launch_bounds__(NW * 64, 1) mh_x3_mt_kernel(MhX3Params p) {
   __shared__ __attribute__((aligned(16))) char lds[TOTAL];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = lane >> 4, j = lane & 15;
+  const int g = lane >> 4;
   const int yi = blockIdx.y;
-  long long c_local[MT];
-  bool valid[MT];
-  sfor<MT>([&](auto m) {
-    c_local[m] = (long long)blockIdx.x * (NW * 16 * MT) + (MT * w + m) * 16 + j;
-    valid[m] = c_local[m] < p.n_chains;
-  });
+  ChainLane ln[MT];
+  sfor<MT>([&](auto m) { ln[m] = chain_lane<NW>(w, lane, p.ch.n_chains, yi, MT, m); });
   EngK e{lds, p.simg, 0, 0, 0, w, lane, g};
-  {
-    const uint4* s2 = (const uint4*)p.sl1;
-    uint4* d2 = (uint4*)(lds + SL1);
-    for (int i = threadIdx.x; i < ST * 32; i += NW * 64) d2[i] = s2[(i >> 5) * 64 + (i & 31)];
-    float* sb = (float*)(lds + SB);
-    for (int i = threadIdx.x; i < 3 * W + 32; i += NW * 64) sb[i] = p.sbias[i];
-    float* yo = (float*)(lds + YO);
-    for (int i = threadIdx.x; i < 32; i += NW * 64) yo[i] = i < kSurYdim ? p.y[(size_t)yi * kSurYdim + i] : 0.0f;
-    __syncthreads();
-    e.start_mid();
-  }
+  stage_surrogate(lds, p, yi);
+  e.start_mid();
   const float* ylds = (const float*)(lds + YO);
   Rng rng[MT];
-  float x[MT][3];
+  float x[MT][3], de[MT];
+  sfor<MT>([&](auto m) { rng[m] = chain_start(p.ch, ln[m], x[m]); });
   bool oor = false;
-  sfor<MT>([&](auto m) {
-    rng[m] = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local[m]), (uint64_t)yi);
-    const long long cc = valid[m] ? c_local[m] : 0;
-    if (p.x_init) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) x[m][d] = p.x_init[((size_t)yi * p.n_chains + cc) * 3 + d];
-    } else {  // torch.rand(n, 3) * 2 - 1 (generate_scatterometry_ground_truth.py:27)
-#pragma unroll
-      for (int d = 0; d < 3; ++d) x[m][d] = (float)(rng_next(rng[m]) >> 8) * 0x1p-24f * 2.0f - 1.0f;
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) oor |= valid[m] && beyond_fp16(x[m][d]);
-  });
   int vmax[MT];  // act_pair's running max (float bits)
   sfor<MT>([&](auto m) { vmax[m] = 0; });
-  f32x4 f[MT][2];
-  sur_forward_mt<MT>(e, x, g, vmax, f);
-  float e0[MT], e_cur[MT];
-  sfor<MT>([&](auto m) { e_cur[m] = e0[m] = mh_energy(f[m], ylds, x[m], p.a, p.b2, p.lam, g); });
-  for (int s = 0; s < p.num_steps; ++s) {
-    float xp[MT][3], u[MT];
+  const auto eval = [&](const float (&xs)[MT][3], float (&es)[MT]) __attribute__((always_inline)) {
     sfor<MT>([&](auto m) {
-      float xi[3];
-      rng_normals<3>(rng[m], xi);
-      u[m] = (float)(rng_next(rng[m]) >> 8) * 0x1p-24f;
 #pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        xp[m][d] = x[m][d] + p.noise_std * xi[d];
-        oor |= valid[m] && beyond_fp16(xp[m][d]);
-      }
+      for (int d = 0; d < 3; ++d) oor |= ln[m].valid && beyond_fp16(xs[m][d]);
     });
-    sur_forward_mt<MT>(e, xp, g, vmax, f);
-    sfor<MT>([&](auto m) {
-      const float e_prop = mh_energy(f[m], ylds, xp[m], p.a, p.b2, p.lam, g);
-      const bool acc = u[m] < expf(-e_prop + e_cur[m]);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) x[m][d] = acc ? xp[m][d] : x[m][d];
-      e_cur[m] = acc ? e_prop : e_cur[m];
-    });
-  }
+    f32x4 f[MT][2];
+    sur_forward_mt<MT>(e, xs, g, vmax, f);
+    sfor<MT>([&](auto m) { es[m] = scat_energy(f[m], ylds, xs[m], p.a, p.b2, p.lam, g); });
+  };
+  random_walk<MT, false>(p.ch, ln, rng, x, de, eval);
   wait_vmcnt<0>();  // the prefetched chunks of a step that never ran land before the workgroup exits
-  sfor<MT>([&](auto m) { oor |= valid[m] && range_bad(vmax[m]); });
+  sfor<MT>([&](auto m) { oor |= ln[m].valid && range_bad(vmax[m]); });
   x3::report_range(oor, p.err, lane);
-  sfor<MT>([&](auto m) {
-    if (valid[m] && g == 0) {
-      float* dst = p.x_out + ((size_t)yi * p.n_chains + c_local[m]) * 3;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) dst[d] = x[m][d];
-      if (p.e_out) p.e_out[(size_t)yi * p.n_chains + c_local[m]] = e_cur[m] - e0[m];
-    }
-  });
+  sfor<MT>([&](auto m) { chain_store(p.ch, ln[m], g, x[m], p.e_out, de[m]); });
 }
 
 // the per-step coefficients: (tau, beta, g, 0), (mean_weight, var, 0, 0) -- the device functions every sampler uses
@@ -1148,13 +1038,12 @@ hipError_t launch_mh_x3(const MhX3Params& p, int n_y, hipStream_t st) {
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, stream_device(st));
     if (n_cu < 1) n_cu = 256;
     auto rounds = [&](int t) {
-      const long long wg = (p.n_chains + dx3::NW * 16 * t - 1) / (dx3::NW * 16 * t) * n_y;
+      const long long wg = (long long)chain_grid(p.ch.n_chains, dx3::NW * 16 * t, n_y).x * n_y;
       return (double)((wg + n_cu - 1) / n_cu);
     };
     mt = rounds(3) * 1.45 < rounds(2) ? 3 : 2;
   }
-  const long long per_wg = dx3::NW * 16 * mt;
-  const dim3 grid((unsigned)((p.n_chains + per_wg - 1) / per_wg), (unsigned)n_y), block(dx3::NW * 64);
+  const dim3 grid = chain_grid(p.ch.n_chains, dx3::NW * 16 * mt, n_y), block(dx3::NW * 64);
   if (mt == 1)
     hipLaunchKernelGGL(dx3::mh_x3_kernel, grid, block, 0, st, p);
   else if (mt == 2)
@@ -1165,7 +1054,6 @@ hipError_t launch_mh_x3(const MhX3Params& p, int n_y, hipStream_t st) {
 }
 
 hipError_t launch_dps_x3(const DpsX3Params& p, int n_y, hipStream_t st) {
-  const long long per_wg = dx3::NW * 16;
   const int S = p.num_steps > 0 ? p.num_steps : 1;
   // one launch-scoped allocation: the stream-ordered image (the kernel's one buffer resource), then the step table
   constexpr size_t kImg = (size_t)dx3::NSTREAM * dx3::CHUNK;
@@ -1186,8 +1074,7 @@ hipError_t launch_dps_x3(const DpsX3Params& p, int n_y, hipStream_t st) {
   DpsX3Params q = p;
   q.img = buf;
   q.coef = (const float*)coef;
-  const dim3 grid((unsigned)((p.n_chains + per_wg - 1) / per_wg), (unsigned)n_y), block(dx3::NW * 64);
-  hipLaunchKernelGGL(dx3::dps_x3_kernel, grid, block, 0, st, q);
+  hipLaunchKernelGGL(dx3::dps_x3_kernel, chain_grid(p.n_chains, dx3::NW * 16, n_y), dim3(dx3::NW * 64), 0, st, q);
   e = hipGetLastError();
   (void)hipFreeAsync(buf, st);
   return e;

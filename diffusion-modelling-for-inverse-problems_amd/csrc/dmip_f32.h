@@ -7,7 +7,7 @@
 //   * a layer's output tile is 16 units x 16 chains: lane (g = l >> 4, j = l & 15) holds units
 //     4g + r (r = 0..3) of chain j. That tile is directly the B operand of 4 k-steps of the next
 //     layer (k-step (q, r) takes register r of tile q), so activations stay in f32 registers.
-//   * weight images (packed by dmip_capi.cpp): k-step (q, r) of output tile o, lane (i, g), holds
+//   * weight images (packed by dmip_capi_pack.cpp): k-step (q, r) of output tile o, lane (i, g), holds
 //     W[16 o + i][16 q + 4 g + r] -- one float4 (ds_read_b128) per lane feeds 4 MFMAs. A 16-row
 //     tile of a W-input layer is one W*64-byte chunk; hidden layers and the output layer are
 //     streamed from L2 through an R-slot LDS ring by LDS-DMA (the bf16 sampler's ring protocol);

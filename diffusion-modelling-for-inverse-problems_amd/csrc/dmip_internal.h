@@ -1,4 +1,4 @@
-// Internal (non-exported) launch interface between the C-ABI layer (dmip_capi.cpp) and the
+// Internal (non-exported) launch interface between the C-ABI layer (dmip_capi_*.cpp) and the
 // kernels (dmip_kernels.hip). Plain structs of device pointers; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,8 +147,21 @@ hipError_t launch_loss_grad(const TrainParams& p, int n_hidden, float* grads, fl
 // Scatterometry surrogate (dmip_surrogate.hip): 3 -> 256 -> 256 -> 256 -> 23 ReLU, exact f32 MFMA.
 constexpr int kSurW = 256, kSurXdim = 3, kSurYdim = 23;
 
+// The chains of a Metropolis / DPS launch over the surrogate, whatever kernel runs them (dmip_mh_chains.h):
+// n_y x n_chains chains, chain c of observation yi keyed (seed, chain_offset + c, yi) in the RNG
+struct MhChains {
+  long long n_chains, chain_offset;  // chains per y; the RNG's chain index of chain 0
+  int num_steps;
+  float noise_std;     // the random-walk proposal's scale (MALA and DPS: unused)
+  unsigned long long seed;
+  const float* x_init; // [n_y][n_chains][3] or null (uniform on [-1, 1]^3 from the RNG)
+  const float* noise;  // injected proposal normals [S][n_y][n_chains][3] or null (exact f32 only)
+  const float* unif;   // injected uniforms [S][n_y][n_chains]
+  float* x_out;        // [n_y][n_chains][3]
+};
+
 struct SurrogateParams {
-  // packed f32 weight images (dmip_capi.cpp pack_surrogate)
+  // packed f32 weight images (dmip_capi_pack.cpp pack_surrogate)
   const float* l1;     // [16 tiles][64 lanes]: W1 | b1 as k = 0..3
   const char* w2;      // [16 tiles][16 q][64][4] forward 256 x 256 images
   const char* w3;
@@ -167,15 +180,7 @@ struct SurrogateParams {
   float* e_out;        // [n]  (MH: [n_y][n_chains] E(x_S) - E(x_0), optional)
   float* g_out;        // [n][3]
   float a, b2, lam;    // noise model a, b^2 and the boundary weight lambda
-  // Metropolis-Hastings
-  long long n_chains, chain_offset;
-  int num_steps;
-  float noise_std;
-  unsigned long long seed;
-  const float* x_init; // [n_y][n_chains][3] or null (uniform on [-1, 1]^3 from the RNG)
-  const float* noise;  // injected proposals [S][n_y][n_chains][3] or null
-  const float* unif;   // injected uniforms  [S][n_y][n_chains]
-  float* x_out;        // [n_y][n_chains][3]
+  MhChains ch;         // Metropolis-Hastings, MALA, DPS
 };
 
 // DPS sampler (config 4): the prior score network MLP2 (x, t) -> x in exact f32 with forward-mode
@@ -195,8 +200,13 @@ struct DpsParams {
 
 hipError_t launch_dps(const DpsParams& p, int n_y, hipStream_t st);
 
+// the grid of a chain kernel: ceil(n_chains / per_wg) workgroups for each of the n_y observations
+inline dim3 chain_grid(long long n_chains, int per_wg, int n_y) {
+  return dim3((unsigned)((n_chains + per_wg - 1) / per_wg), (unsigned)n_y);
+}
+
 // DPS at fp32 accuracy on the fp16 matrix rate (dmip_dps_x3.hip): x3-split images of the prior (MLP2 [256]^3, x 3)
-// and of the surrogate, packed by dmip_capi.cpp (pack_dps_x3_prior / pack_dps_x3_surrogate)
+// and of the surrogate, packed by dmip_capi_pack.cpp (pack_dps_x3_prior / pack_dps_x3_surrogate)
 constexpr int kDpsX3Chunk = 32768;
 constexpr int kDpsX3PriorChunks = 35;  // P2 (8) | P3 (8) | Pout (1) | P4^T (1) | P3^T (8) | P2^T (8) | P1^T (1)
 constexpr int kDpsX3SurChunks = 35;    // S2 (8) | S3 (8) | Sout (1) | S4^T (1) | S3^T (8) | S2^T (8) | S1^T (1)
@@ -228,12 +238,8 @@ struct MhX3Params {
   const char* sl1;      // its layer 1 over x, split: [16][64][8] fp16
   const float* sbias;   // b1 | b2 | b3 [256] | b4 [32]
   const float* y;       // [n_y][23]
-  long long n_chains, chain_offset;
-  int num_steps;
-  float noise_std, a, b2, lam;
-  unsigned long long seed;
-  const float* x_init;  // [n_y][n_chains][3] or null (x0 ~ U[-1, 1]^3 from the chain RNG)
-  float* x_out;         // [n_y][n_chains][3]
+  MhChains ch;          // no injected draws
+  float a, b2, lam;
   float* e_out;         // [n_y][n_chains] E(x_S) - E(x_0), or null
   unsigned int* err;    // device status word (kErrRange)
 };
@@ -243,8 +249,8 @@ hipError_t launch_surrogate_eval(const SurrogateParams& p, int mode, int n_wg, h
 int surrogate_rows_per_wg();
 hipError_t launch_mh(const SurrogateParams& p, int n_y, hipStream_t st);
 
-// Metropolis-adjusted Langevin (dmip_surrogate.hip mala_kernel): the MH fields of `s` (s.noise / s.unif the injected
-// eta [S][L][n_y][n_chains][3] / u [S][n_y][n_chains]; s.noise_std unused) plus the Langevin proposal's constants
+// Metropolis-adjusted Langevin (dmip_surrogate.hip mala_kernel): the chains of `s` (s.ch.noise / s.ch.unif the injected
+// eta [S][L][n_y][n_chains][3] / u [S][n_y][n_chains]) plus the Langevin proposal's constants
 struct MalaParams {
   SurrogateParams s;
   int lang_steps;      // L Langevin sub-steps per Metropolis step
@@ -254,7 +260,7 @@ struct MalaParams {
 };
 hipError_t launch_mala(const MalaParams& p, int n_y, hipStream_t st);
 
-// Exact-f32 networks (dmip_f32.hip, DMIP_PREC_F32): images packed by dmip_capi.cpp pack_f32_net.
+// Exact-f32 networks (dmip_f32.hip, DMIP_PREC_F32): images packed by dmip_capi_pack.cpp pack_f32_net.
 struct F32Net {
   const float* l1;     // [W/16 tiles][K1Q][64]: layer 1 over every input column, then the bias column
   const char* stream;  // [(L-1) W/16 hidden tiles + OT output tiles][W/16 q][64][4] floats
@@ -362,7 +368,7 @@ bool f32_heun_supported(int mode, int width, int n_hidden, int xdim, int act);
 hipError_t launch_f32_forward(const F32ForwardParams& p, int width, int ot, hipStream_t st, bool* supported);
 hipError_t launch_f32_l1_prep(const F32L1PrepParams& p, int n_y, hipStream_t st);
 
-// fp32-accurate split-fp16 networks (dmip_x3.h, DMIP_PREC_F32X3): images packed by dmip_capi.cpp pack_x3_net.
+// fp32-accurate split-fp16 networks (dmip_x3.h, DMIP_PREC_F32X3): images packed by dmip_capi_pack.cpp pack_x3_net.
 struct X3Net {
   const char* l1;      // [W/16 tiles][K1Q][64 lanes][8 fp16]: layer-1 image (x, t columns -- or every column, CDiffE)
   const char* stream;  // [(L-1) NCH hidden chunks + 1 output chunk][CHUNK bytes] (dmip_x3.h Shape)

@@ -23,13 +23,12 @@
 //     pass kept as bits (2 VGPRs per layer).
 #include "dmip_device.h"
 #include "dmip_internal.h"
+#include "dmip_mh_chains.h"
 
 #include <type_traits>
 
 namespace dmip {
 namespace sg {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int W = kSurW;           // 256
 constexpr int ST = W / 16;         // 16 output tiles per 256-wide layer
@@ -249,6 +248,11 @@ struct Engine {
 //       + lambda sum_d relu(x_d - 1) + relu(-1 - x_d)
 // The 23 output rows are spread over the 4 lane groups of a chain: partial sums, then two xor
 // shuffles. v = dE/df_k for the reverse pass (rows >= 23 zero).
+// KEEP IN STEP with scat_energy (dmip_mh_chains.h), its value-only form for the Metropolis kernels: the same operations
+// in the same order. Shared forms tried (this function calling scat_energy's row loop as a template on want_v, or with
+// want_v at run time, from the header or through a wrapper here): surrogate_eval_kernel<1>, <2> changed their code in
+// each; with the shuffles behind a forceinline wrapper they kept it, but the fp32x3 two-tile MH kernel then ran 1.2 %
+// slower than before in two sessions (profiles/mh_chains/README.md).
 __device__ __forceinline__ float energy(const f32x4 (&f)[2], const float* y, const float (&x)[XD], float a,
                                         float b2, float lam, int g, f32x4 (&v)[2], bool want_v) {
   float slog = 0.0f, ssq = 0.0f;
@@ -386,13 +390,9 @@ __global__ void __launch_bounds__(NW * 64, 1) surrogate_eval_kernel(SurrogatePar
 }
 
 // ------------------------------------------------------------------- Metropolis-Hastings kernel
-// anneal_to_energy (models/SNF.py:250-275) without Langevin proposals: per step
-//   x_prop = x + noise_std * xi;  accept iff u < exp(-E(x_prop) + E(x))
-// with E the negative log posterior above for this workgroup's y. The chain state (x, E(x), RNG)
-// stays in registers for all steps (every lane of a chain carries an identical copy); E(x) is
-// carried instead of being recomputed (the reference's energy(x_curr) is the same value).
-// Outputs x and E(x_final) - E(x_0) (the reference's second return value).
-// INJECT: xi [S][n_y][n][3] and u [S][n_y][n] replace the RNG (replaying captured draws).
+// anneal_to_energy (models/SNF.py:250-275) without Langevin proposals, with E the negative log posterior for this
+// workgroup's y: the chain life cycle and the step loop of dmip_mh_chains.h on the exact-f32 forward pass.
+// Outputs x and E(x_final) - E(x_0). INJECT: captured draws replace the RNG (random_walk).
 template <bool INJECT>
 __global__ void __launch_bounds__(NW * 64, 1) mh_kernel(SurrogateParams p) {
   __shared__ __attribute__((aligned(16))) char lds[RING_OFF_FWD + R * CHUNK];
@@ -400,58 +400,24 @@ __global__ void __launch_bounds__(NW * 64, 1) mh_kernel(SurrogateParams p) {
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4;
   const int yi = blockIdx.y;
-  const long long c_local = (long long)blockIdx.x * (NW * 16) + w * 16 + (lane & 15);
-  const bool valid = c_local < p.n_chains;
-  const long long cc = valid ? c_local : 0;
+  const ChainLane ln[1] = {chain_lane<NW>(w, lane, p.ch.n_chains, yi)};
   Engine<false, RING_OFF_FWD, PlanFwd> eng{lds, make_plan<PlanFwd>(p), 0, w, lane, g};
   float* ylds = (float*)(lds + Y_OFF);
-  for (int i = threadIdx.x; i < 32; i += NW * 64) ylds[i] = i < YD ? p.y[(size_t)yi * YD + i] : 0.0f;
+  stage_y<NW>(ylds, p.y, yi);
   eng.prologue(p);
 
-  Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
-  float x[XD];
-  if (p.x_init) {
-#pragma unroll
-    for (int d = 0; d < XD; ++d) x[d] = p.x_init[((size_t)yi * p.n_chains + cc) * XD + d];
-  } else {
-    // torch.rand(n, 3) * 2 - 1 (generate_scatterometry_ground_truth.py:27)
-#pragma unroll
-    for (int d = 0; d < XD; ++d) x[d] = (float)(rng_next(rng) >> 8) * 0x1p-24f * 2.0f - 1.0f;
-  }
-  f32x4 f[2], v[2];
-  uint32_t m[3][2];
-  eng.forward(x, f, m);
-  const float e0 = energy(f, ylds, x, p.a, p.b2, p.lam, g, v, false);
-  float e_cur = e0;
-  const size_t plane = (size_t)gridDim.y * p.n_chains;
-  for (int s = 0; s < p.num_steps; ++s) {
-    float xi[XD], u;
-    if constexpr (INJECT) {
-      const float* src = p.noise + ((size_t)s * plane + (size_t)yi * p.n_chains + cc) * XD;
-#pragma unroll
-      for (int d = 0; d < XD; ++d) xi[d] = src[d];
-      u = p.unif[(size_t)s * plane + (size_t)yi * p.n_chains + cc];
-    } else {
-      rng_normals<XD>(rng, xi);
-      u = (float)(rng_next(rng) >> 8) * 0x1p-24f;
-    }
-    float xp[XD];
-#pragma unroll
-    for (int d = 0; d < XD; ++d) xp[d] = x[d] + p.noise_std * xi[d];
-    eng.forward(xp, f, m);
-    const float e_prop = energy(f, ylds, xp, p.a, p.b2, p.lam, g, v, false);
-    const bool acc = u < expf(-e_prop + e_cur);
-#pragma unroll
-    for (int d = 0; d < XD; ++d) x[d] = acc ? xp[d] : x[d];
-    e_cur = acc ? e_prop : e_cur;
-  }
+  float x[1][XD], de[1];
+  Rng rng[1] = {chain_start(p.ch, ln[0], x[0])};
+  // (always inlined, as every eval of random_walk: an outlined call would put the forward pass's arrays on the stack)
+  const auto eval = [&](const float (&xs)[1][XD], float (&es)[1]) __attribute__((always_inline)) {
+    f32x4 f[2];
+    uint32_t m[3][2];
+    eng.forward(xs[0], f, m);
+    es[0] = scat_energy(f, ylds, xs[0], p.a, p.b2, p.lam, g);
+  };
+  random_walk<1, INJECT>(p.ch, ln, rng, x, de, eval);
   eng.epilogue();
-  if (valid && g == 0) {
-    float* dst = p.x_out + ((size_t)yi * p.n_chains + c_local) * XD;
-#pragma unroll
-    for (int d = 0; d < XD; ++d) dst[d] = x[d];
-    if (p.e_out) p.e_out[(size_t)yi * p.n_chains + c_local] = e_cur - e0;
-  }
+  chain_store(p.ch, ln[0], g, x[0], p.e_out, de[0]);
 }
 
 // ------------------------------------------------------- Metropolis-adjusted Langevin kernel
@@ -490,6 +456,10 @@ __device__ __forceinline__ float interp_energy_grad(E& eng, const float* ylds, c
 // would turn 0 * inf into NaN. Outputs x, E_l(x_S) - E_l(x_0) and the number of accepted steps.
 // Product RNG per step: L x rng_normals<3>, then one word for u. INJECT: eta [S][L][n_y][n][3] and
 // u [S][n_y][n] replace it (replaying the reference's captured draws).
+// Of dmip_mh_chains.h's life cycle this kernel takes chain_lane and uniform01; y's staging, the start and the store
+// stay written out. It sits at 256 VGPRs with 104 / 108 B of scratch (product RNG / injected draws), and every other
+// helper moved that: all of them 112 / 116 B, stage_y alone 108 / 108, chain_lane + chain_start 108 / 108,
+// chain_lane + chain_store 116 / 116.
 template <bool INJECT>
 __global__ void __launch_bounds__(NW * 64, 1) mala_kernel(MalaParams q) {
   const SurrogateParams& p = q.s;
@@ -498,30 +468,27 @@ __global__ void __launch_bounds__(NW * 64, 1) mala_kernel(MalaParams q) {
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4;
   const int yi = blockIdx.y;
-  const long long c_local = (long long)blockIdx.x * (NW * 16) + w * 16 + (lane & 15);
-  const bool valid = c_local < p.n_chains;
-  const long long cc = valid ? c_local : 0;
+  const ChainLane ln = chain_lane<NW>(w, lane, p.ch.n_chains, yi);
   Engine<true, RING_OFF_GRAD, PlanGrad> eng{lds, make_plan<PlanGrad>(p), 0, w, lane, g};
   float* ylds = (float*)(lds + Y_OFF);
   for (int i = threadIdx.x; i < 32; i += NW * 64) ylds[i] = i < YD ? p.y[(size_t)yi * YD + i] : 0.0f;
   eng.prologue(p);
 
-  Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
+  Rng rng = rng_init(p.ch.seed, (uint64_t)(p.ch.chain_offset + ln.c), (uint64_t)yi);
   float x[XD];
-  if (p.x_init) {
+  if (p.ch.x_init) {
 #pragma unroll
-    for (int d = 0; d < XD; ++d) x[d] = p.x_init[((size_t)yi * p.n_chains + cc) * XD + d];
+    for (int d = 0; d < XD; ++d) x[d] = p.ch.x_init[ln.at(p.ch.n_chains) * XD + d];
   } else {
 #pragma unroll
-    for (int d = 0; d < XD; ++d) x[d] = (float)(rng_next(rng) >> 8) * 0x1p-24f * 2.0f - 1.0f;
+    for (int d = 0; d < XD; ++d) x[d] = uniform01(rng) * 2.0f - 1.0f;
   }
   float g_cur[XD];
   const float e0 = interp_energy_grad(eng, ylds, q, x, g_cur);
   float e_cur = e0;
   int n_acc = 0;
-  const size_t plane = (size_t)gridDim.y * p.n_chains;
-  const size_t at = (size_t)yi * p.n_chains + cc;
-  for (int s = 0; s < p.num_steps; ++s) {
+  const size_t plane = (size_t)gridDim.y * p.ch.n_chains, at = ln.at(p.ch.n_chains);
+  for (int s = 0; s < p.ch.num_steps; ++s) {
     float xx[XD], gg[XD], ld = 0.0f, e_y = e_cur;
 #pragma unroll
     for (int d = 0; d < XD; ++d) xx[d] = x[d], gg[d] = g_cur[d];
@@ -529,7 +496,7 @@ __global__ void __launch_bounds__(NW * 64, 1) mala_kernel(MalaParams q) {
     for (int l = 0; l < q.lang_steps; ++l) {
       float eta[XD];
       if constexpr (INJECT) {
-        const float* src = p.noise + (((size_t)s * q.lang_steps + l) * plane + at) * XD;
+        const float* src = p.ch.noise + (((size_t)s * q.lang_steps + l) * plane + at) * XD;
 #pragma unroll
         for (int d = 0; d < XD; ++d) eta[d] = src[d];
       } else {
@@ -552,8 +519,8 @@ __global__ void __launch_bounds__(NW * 64, 1) mala_kernel(MalaParams q) {
       asm volatile("" : "+v"(ld), "+v"(e_y));
     }
     float u;
-    if constexpr (INJECT) u = p.unif[(size_t)s * plane + at];
-    else u = (float)(rng_next(rng) >> 8) * 0x1p-24f;
+    if constexpr (INJECT) u = p.ch.unif[(size_t)s * plane + at];
+    else u = uniform01(rng);
     const bool acc = u < expf(-e_y + e_cur + ld);
 #pragma unroll
     for (int d = 0; d < XD; ++d) {
@@ -564,8 +531,8 @@ __global__ void __launch_bounds__(NW * 64, 1) mala_kernel(MalaParams q) {
     n_acc += acc ? 1 : 0;
   }
   eng.epilogue();
-  if (valid && g == 0) {
-    float* dst = p.x_out + at * XD;
+  if (ln.valid && g == 0) {
+    float* dst = p.ch.x_out + at * XD;
 #pragma unroll
     for (int d = 0; d < XD; ++d) dst[d] = x[d];
     if (p.e_out) p.e_out[at] = e_cur - e0;
@@ -690,7 +657,7 @@ __global__ void __launch_bounds__(NW * 64, 1) dps_kernel(DpsParams p) {
   const int g = lane >> 4, j = lane & 15;
   const int yi = blockIdx.y;
   const long long c_local = (long long)blockIdx.x * (NW * 16) + w * 16 + j;
-  const bool valid = c_local < p.s.n_chains;
+  const bool valid = c_local < p.s.ch.n_chains;
   Engine<true, RING_OFF_DPS, PlanDps> eng{
       lds, PlanDps{p.pw2, p.pw3, make_plan<PlanGrad>(p.s)}, 0, w, lane, g};
   float* ylds = (float*)(lds + Y_OFF);
@@ -705,7 +672,7 @@ __global__ void __launch_bounds__(NW * 64, 1) dps_kernel(DpsParams p) {
   }
   float* sj = (float*)(lds + SJ_OFF) + w * 256;  // [16 chains][m][r]
 
-  Rng rng = rng_init(p.s.seed, (uint64_t)(p.s.chain_offset + c_local), (uint64_t)yi);
+  Rng rng = rng_init(p.s.ch.seed, (uint64_t)(p.s.ch.chain_offset + c_local), (uint64_t)yi);
   float x[XD];
   {
     float n0[XD];
@@ -713,8 +680,8 @@ __global__ void __launch_bounds__(NW * 64, 1) dps_kernel(DpsParams p) {
 #pragma unroll
     for (int d = 0; d < XD; ++d) x[d] = __fadd_rn(__fmul_rn(n0[d], p.stdv), p.mean);
   }
-  for (int i = 0; i < p.s.num_steps; ++i) {
-    const StepCoef cf = step_coef(i, p.s.num_steps, p.T, p.bmin, p.bdiff);
+  for (int i = 0; i < p.s.ch.num_steps; ++i) {
+    const StepCoef cf = step_coef(i, p.s.ch.num_steps, p.T, p.bmin, p.bdiff);
     // prior score and Jacobian, 4 chains per pass
     const int m = lane & 3;
 #pragma unroll 1
@@ -783,7 +750,7 @@ __global__ void __launch_bounds__(NW * 64, 1) dps_kernel(DpsParams p) {
   }
   eng.epilogue();
   if (valid && g == 0) {
-    float* dst = p.s.x_out + ((size_t)yi * p.s.n_chains + c_local) * XD;
+    float* dst = p.s.ch.x_out + ((size_t)yi * p.s.ch.n_chains + c_local) * XD;
 #pragma unroll
     for (int d = 0; d < XD; ++d) dst[d] = x[d];
   }
@@ -804,16 +771,13 @@ hipError_t launch_surrogate_eval(const SurrogateParams& p, int mode, int n_wg, h
 int surrogate_rows_per_wg() { return sg::NW * 16; }
 
 hipError_t launch_dps(const DpsParams& p, int n_y, hipStream_t st) {
-  const long long per_wg = sg::NW * 16;
-  const dim3 grid((unsigned)((p.s.n_chains + per_wg - 1) / per_wg), (unsigned)n_y), block(sg::NW * 64);
-  hipLaunchKernelGGL(sg::dps_kernel, grid, block, 0, st, p);
+  hipLaunchKernelGGL(sg::dps_kernel, chain_grid(p.s.ch.n_chains, sg::NW * 16, n_y), dim3(sg::NW * 64), 0, st, p);
   return hipGetLastError();
 }
 
 hipError_t launch_mh(const SurrogateParams& p, int n_y, hipStream_t st) {
-  const long long per_wg = sg::NW * 16;
-  const dim3 grid((unsigned)((p.n_chains + per_wg - 1) / per_wg), (unsigned)n_y), block(sg::NW * 64);
-  if (p.noise)
+  const dim3 grid = chain_grid(p.ch.n_chains, sg::NW * 16, n_y), block(sg::NW * 64);
+  if (p.ch.noise)
     hipLaunchKernelGGL(sg::mh_kernel<true>, grid, block, 0, st, p);
   else
     hipLaunchKernelGGL(sg::mh_kernel<false>, grid, block, 0, st, p);
@@ -821,9 +785,8 @@ hipError_t launch_mh(const SurrogateParams& p, int n_y, hipStream_t st) {
 }
 
 hipError_t launch_mala(const MalaParams& q, int n_y, hipStream_t st) {
-  const long long per_wg = sg::NW * 16;
-  const dim3 grid((unsigned)((q.s.n_chains + per_wg - 1) / per_wg), (unsigned)n_y), block(sg::NW * 64);
-  if (q.s.noise)
+  const dim3 grid = chain_grid(q.s.ch.n_chains, sg::NW * 16, n_y), block(sg::NW * 64);
+  if (q.s.ch.noise)
     hipLaunchKernelGGL(sg::mala_kernel<true>, grid, block, 0, st, q);
   else
     hipLaunchKernelGGL(sg::mala_kernel<false>, grid, block, 0, st, q);

@@ -16,7 +16,7 @@
 //     the host maps to unit kperm16(q, g, m) = 32 q + 16 (m >> 2) + 4 g + (m & 3) of the weight image.
 //   * activations stay in registers as (hi, lo) fp16 pairs: W/32 B fragments each (W = 256: 64 VGPRs
 //     for a layer's input, 64 for its output), so a 512-thread workgroup keeps 2 waves per SIMD.
-//   * weight images (dmip_capi.cpp pack_x3_net): output tile o, k-step q, part p (hi / lo), lane
+//   * weight images (dmip_capi_pack.cpp pack_x3_net): output tile o, k-step q, part p (hi / lo), lane
 //     l = i + 16 g holds A[16 o + i][kperm16(q, g, 0..7)] -- one ds_read_b128 per lane per fragment;
 //     a tile is W/16 KiB (both parts). The W x W layers and the output layer stream from L2 through
 //     an R-slot LDS ring by LDS-DMA (the protocol of dmip_f32.h), CHUNK = CT tiles (<= 32 KiB);

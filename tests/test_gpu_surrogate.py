@@ -145,19 +145,46 @@ def test_mh_product_rng_vs_oracle(dmip, golden, fm, precision):
     assert same.mean() >= 0.95, same.mean()
 
 
-@pytest.mark.parametrize("n", [1, 17, 129, 257])
-def test_mh_fp32x3_ragged_chain_counts_vs_oracle(dmip, golden, fm, n):
-    """The multi-tile MH kernel (two 16-chain tiles per wave, 128 chains per workgroup) on chain counts that leave
-    partial tiles and idle waves, over two ys: chain by chain against the oracle (30 steps)."""
+# (the fp32x3 cases keep their ids "1" .. "257"; the exact-f32 ones are "fp32-1" .. "fp32-257")
+@pytest.mark.parametrize("precision,n", [pytest.param("fp32x3", n, id=str(n)) for n in (1, 17, 129, 257)] +
+                         [pytest.param("fp32", n, id=f"fp32-{n}") for n in (1, 17, 129, 257)])
+def test_mh_fp32x3_ragged_chain_counts_vs_oracle(dmip, golden, fm, precision, n):
+    """The multi-tile MH kernel (two 16-chain tiles per wave, 128 chains per workgroup) and the exact-f32 one (one tile,
+    128 chains per workgroup) on chain counts that leave partial tiles and idle waves, over two ys: chain by chain
+    against the oracle (30 steps). The exact-f32 cases pin the kernel on the shared chain driver to the kernel before
+    it: that one met the same share at every n with seed n, so no seed was changed."""
     model, pr, params = fm
     ys = golden("data_scat.npz")["y_test"][7:9]
     x = pr.mh_sample(model, {"a": 0.2, "b": 0.01, "lambd_bd": 1000}, torch.from_numpy(ys), n, 30, 0.5, seed=n,
-                     precision="fp32x3").cpu().numpy()
+                     precision=precision).cpu().numpy()
     assert x.shape == (2, n, 3) and np.all(np.isfinite(x))
     for k in range(2):
         ref, _ = O.mh_sample(params, ys[k], 30, 0.5, seed=n, n_chains=n, stream=k)
         same = np.all(np.abs(x[k] - ref) <= 1e-5, axis=1)
         assert same.mean() >= (0.95 if n >= 17 else 1.0), (k, same.mean())
+
+
+def test_mh_fp32x3_tile_variants_bit_identical_at_small_counts(dmip, golden, fm, tmp_path):
+    """The one-tile and the three-tile fp32x3 kernel (DMIP_MH_MT=1, 3: the knob is read once per process, so a fresh
+    child process each, one after the other) against this process's launch, which picks two tiles at these sizes:
+    tests/mh_tiles.py's runs. x and E(x_S) - E(x_0) of all three are the same bits (one RNG stream, start, step loop and
+    store: dmip_mh_chains.h)."""
+    import subprocess
+    import sys
+    import mh_tiles
+    assert "DMIP_MH_MT" not in os.environ
+    model, pr, _ = fm
+    here = mh_tiles.runs(pr, model, golden("data_scat.npz")["y_test"][7:9])
+    assert len(here) == 12 and all(np.all(np.isfinite(v)) for v in here.values())
+    for mt in ("1", "3"):
+        out = str(tmp_path / f"mt{mt}.npz")
+        r = subprocess.run([sys.executable, os.path.join(mh_tiles.ROOT, "tests", "mh_tiles.py"), out],
+                           env=dict(os.environ, DMIP_MH_MT=mt), capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        z = np.load(out)
+        assert sorted(z.files) == sorted(here)
+        diff = [k for k in here if z[k].tobytes() != here[k].tobytes()]
+        assert not diff, (mt, diff)
 
 
 def test_mh_fp32x3_three_tile_launch_matches_two_tile(dmip, golden, fm):

@@ -70,7 +70,7 @@ def test_bf16_samplers_have_no_scratch(isa):
 # The fp32x3 flow kernels: none at any width, which is what justifies compiling width 512.
 _SCRATCH_CAP = {"x3_sampler_kernel": 0, "x3k_sampler_kernel": 128, "loss_grad_kernel": 0, "x3p_sampler_kernel": 0,
                 "dps_x3_kernel": 0, "mh_x3_kernel": 0, "mh_x3_mt_kernel": 0, "x3_flow_kernel": 0,
-                "x3_flow_sample_kernel": 0}
+                "x3_flow_sample_kernel": 0, "mh_kernel": 0}
 # The config-5 forward half (loss_grad_kernel<NL, 1>, two waves per SIMD, 256 registers) writes the record reverse half's
 # per-layer records since round 6: about 26 dwords of its state spill (104-112 B), reloaded once per tile; the kernel
 # without the record writes has none
