@@ -102,6 +102,16 @@ def joint_fused_config(model, loss_fn):
     return cfg
 
 
+def model_vpsde(model):
+    """The dmip_vpsde of a model: its base SDE's beta_min / beta_max with the reverse SDE's T, as the samplers build
+    it (estimators._prepare), and the same ValueError when the two objects disagree on T. dmip_train_draws draws t on
+    [t_add, T]; the loss kernels read beta_min / beta_max only."""
+    base = model.sde.base_sde
+    if float(base.T) != float(model.sde.T):
+        raise ValueError("PluginReverseSDE.T must equal the base SDE's T")
+    return _lib.vpsde(base.beta_min, base.beta_max, model.sde.T)
+
+
 def fused_loss_grad(model, loss_fn, cfg, x, y, t, eps, precision=None):
     """One fused loss + gradient evaluation. Returns (loss, info) like the reference loss objects:
     a 0-d tensor and {component name: 0-d tensor}. precision: "fp32" (dmip_loss_grad_f32, default) or
@@ -118,8 +128,7 @@ def fused_loss_grad(model, loss_fn, cfg, x, y, t, eps, precision=None):
         params = list(net.parameters())
         flat = torch.empty(sum(p.numel() for p in params), **f32)
         out = torch.empty(4, **f32)
-        base = model.sde.base_sde
-        sde = _lib.vpsde(base.beta_min, base.beta_max, 1.0)
+        sde = model_vpsde(model)
         _lib.loss_grad_f32(layers, net.input_dim, net.output_dim, x.shape[1], sde, cfg, x, x, t, eps, flat, out)
         _set_grads(params, flat)
         return loss_info(cfg.kind, out)
@@ -129,8 +138,7 @@ def fused_loss_grad(model, loss_fn, cfg, x, y, t, eps, precision=None):
     params = list(net.parameters())
     flat = torch.empty(sum(p.numel() for p in params), **f32)
     out = torch.empty(4, **f32)
-    base = model.sde.base_sde
-    sde = _lib.vpsde(base.beta_min, base.beta_max, 1.0)
+    sde = model_vpsde(model)
     has_ic = cfg.kind in (_lib.DMIP_LOSS_PINN, _lib.DMIP_LOSS_PINN2)
     precision = precision or train_precision()
     widths = [int(w.shape[0]) for w, _ in layers[:-1]]
@@ -291,7 +299,7 @@ class DeviceTrainStep:
         self.wp = (ctypes.c_void_p * (L + 1))(*[w.data_ptr() for w, _ in layers])
         self.bp = (ctypes.c_void_p * (L + 1))(*[b.data_ptr() for _, b in layers])
         base = model.sde.base_sde
-        self.sde = _lib.vpsde(base.beta_min, base.beta_max, 1.0)
+        self.sde = model_vpsde(model)
         self.t_eps = float(getattr(base, "t_epsilon", 1e-3))
         self.debias = bool(model.sde.debias)
         widths = [int(w.shape[0]) for w, _ in layers[:-1]]
@@ -503,10 +511,9 @@ def posterior_loss_grad(model, loss_fn, x, y, t, eps, want_target=False):
     gl = torch.empty(sum(p.numel() for p in lp), **f32)
     out = torch.empty(3, **f32)
     tgt = torch.empty_like(x) if want_target else None
-    base = model.sde.base_sde
     sur = surrogate_handle(loss_fn.forward_model, dev)
     _lib.posterior_loss_grad(pl, ll, sur, _lib.scat_noise(loss_fn.a, loss_fn.b, 0.0), loss_fn.lam,
-                             _lib.vpsde(base.beta_min, base.beta_max, 1.0), x, y, t, eps, gp, gl, out, tgt)
+                             model_vpsde(model), x, y, t, eps, gp, gl, out, tgt)
     for params, flat in ((pp, gp), (lp, gl)):
         off = 0
         for p in params:

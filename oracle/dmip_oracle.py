@@ -136,11 +136,11 @@ def mlp2_a(params, x, t, act="tanh"):
     return mlp_forward(params, np.concatenate([x, t], axis=1), act=act)
 
 
-def posterior_a(prior_params, lik_params, x, y, t, act="tanh"):
-    """PosteriorScore.forward (nets.py:155-157): g(t) * (prior(x,t) + lik(x,y,t))."""
+def posterior_a(prior_params, lik_params, x, y, t, act="tanh", beta_min=BETA_MIN, beta_max=BETA_MAX):
+    """PosteriorScore.forward (nets.py:155-157): g(t) * (prior(x,t) + lik(x,y,t)), g of the given VP-SDE."""
     s = (mlp2_a(prior_params, x, t, act=act) + cde_a(lik_params, x, y, t, act=act)).astype(F32)
     tt = np.broadcast_to(np.asarray(t, F32).reshape(-1, 1), s.shape)
-    return (vp_g(tt) * s).astype(F32)
+    return (vp_g(tt, beta_min, beta_max) * s).astype(F32)
 
 
 # ------------------------------------------------------------------------------------------
@@ -312,26 +312,27 @@ def em_sample(a_fn, x0, num_steps, T=1.0, noise=None, rng_state=None, xdim=None,
 
 
 def cde_sample(params, y, num_samples, num_steps, seed, mean=0.0, std=1.0, chain_offset=0,
-               stream=0, T=1.0, snapshots=None, act="tanh"):
+               stream=0, T=1.0, snapshots=None, act="tanh", beta_min=BETA_MIN, beta_max=BETA_MAX):
     """Product-RNG CDE sampler: x0 = normals*std + mean (models/diffusion.py:32-33), then EM."""
     xdim = params[-1][0].shape[0]
     st = rng_init(seed, np.arange(chain_offset, chain_offset + num_samples), stream)
     x0 = (rng_normals(st, xdim) * F32(std) + F32(mean)).astype(F32)
     y = np.asarray(y, F32)
     return em_sample(lambda x, tau: cde_a(params, x, y, tau, act=act), x0, num_steps, T=T,
-                     rng_state=st, xdim=xdim, snapshots=snapshots)
+                     rng_state=st, xdim=xdim, snapshots=snapshots, beta_min=beta_min, beta_max=beta_max)
 
 
 def posterior_sample(prior_params, lik_params, y, num_samples, num_steps, seed, mean=0.0, std=1.0,
-                     chain_offset=0, stream=0, T=1.0, act="tanh"):
+                     chain_offset=0, stream=0, T=1.0, act="tanh", beta_min=BETA_MIN, beta_max=BETA_MAX):
     """Product-RNG PosteriorDiffusionEstimator sampler (models/diffusion.py:27-46 with the
     PosteriorScore drift a = g (prior + lik), nets.py:155-157): same RNG consumption as CDE."""
     xdim = lik_params[-1][0].shape[0]
     st = rng_init(seed, np.arange(chain_offset, chain_offset + num_samples), stream)
     x0 = (rng_normals(st, xdim) * F32(std) + F32(mean)).astype(F32)
     y = np.asarray(y, F32)
-    return em_sample(lambda x, tau: posterior_a(prior_params, lik_params, x, y, tau, act=act), x0, num_steps, T=T,
-                     rng_state=st, xdim=xdim)
+    sde = dict(beta_min=beta_min, beta_max=beta_max)  # (the drift's own g and the EM step's: one SDE)
+    return em_sample(lambda x, tau: posterior_a(prior_params, lik_params, x, y, tau, act=act, **sde), x0, num_steps,
+                     T=T, rng_state=st, xdim=xdim, **sde)
 
 
 def cdiffe_sample(params, y, num_samples, num_steps, seed, mean=0.0, std=1.0, chain_offset=0, stream=0,

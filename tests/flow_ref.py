@@ -48,18 +48,20 @@ def score_div(params, x, y, tau, g, prior_params=None, dtype=np.float64):
     return a.astype(dtype), dv.astype(dtype)
 
 
-def flow_grid(num_steps, T=1.0, dtype=np.float64):
-    """tau_k, beta_k, g_k (k = 0..S) and h: the f32 linspace of the sampler's schedule, the rest in `dtype`."""
+def flow_grid(num_steps, T=1.0, dtype=np.float64, beta_min=O.BETA_MIN, beta_max=O.BETA_MAX):
+    """tau_k, beta_k, g_k (k = 0..S) and h: the f32 linspace of the sampler's schedule, the rest in `dtype` (bmin and
+    bdiff = beta_max - beta_min, taken in double, each rounded to `dtype` once, as flow_coef does)."""
     tau = (O.linspace_f32(num_steps) * np.float32(T)).astype(np.float32).astype(dtype)
-    beta = dtype(O.BETA_MIN) + dtype(O.BETA_MAX - O.BETA_MIN) * tau
+    beta = dtype(beta_min) + dtype(beta_max - beta_min) * tau
     return tau, beta.astype(dtype), np.sqrt(beta).astype(dtype), dtype(T / num_steps)
 
 
-def log_prob(params, x, y, num_steps, prior_params=None, T=1.0, dtype=np.float64):
+def log_prob(params, x, y, num_steps, prior_params=None, T=1.0, dtype=np.float64, beta_min=O.BETA_MIN,
+             beta_max=O.BETA_MAX):
     """(logp (n,) float64, latent x_S (n, d) in dtype) of rows x (n, d) under one observation y."""
     x = np.asarray(x, dtype)
     n, d = x.shape
-    tau, beta, g, h = flow_grid(num_steps, T, dtype)
+    tau, beta, g, h = flow_grid(num_steps, T, dtype, beta_min, beta_max)
     half = dtype(0.5)
     I = np.zeros(n, np.float64)
     for k in range(num_steps):
@@ -76,7 +78,7 @@ def log_prob(params, x, y, num_steps, prior_params=None, T=1.0, dtype=np.float64
     return -0.5 * d * LOG_2PI - 0.5 * (xs * xs).sum(1) + I, x
 
 
-def ode_sample(params, x0, y, num_steps, prior_params=None, T=1.0):
+def ode_sample(params, x0, y, num_steps, prior_params=None, T=1.0, beta_min=O.BETA_MIN, beta_max=O.BETA_MAX):
     """The sampler's Euler loop at lmbd = 1 in float64 (models/diffusion.py:38-42 with sdes.py:77-87): from the
     latent x0 back to data space; the round trip's other half."""
     x = np.asarray(x0, np.float64)
@@ -84,22 +86,22 @@ def ode_sample(params, x0, y, num_steps, prior_params=None, T=1.0):
     delta = T / num_steps
     for i in range(num_steps):
         tau = T - ts[i]
-        beta = O.BETA_MIN + (O.BETA_MAX - O.BETA_MIN) * tau
+        beta = beta_min + (beta_max - beta_min) * tau
         g = np.sqrt(beta)
         a, _ = score_div(params, x, y, tau, g, prior_params, np.float64)
         x = x + delta * (0.5 * g * a + 0.5 * beta * x)
     return x
 
 
-def lmbd_step_f32(x, a, xi, tau, delta, lmbd):
+def lmbd_step_f32(x, a, xi, tau, delta, lmbd, beta_min=O.BETA_MIN, beta_max=O.BETA_MAX):
     """One reverse step's mu, sigma and x_next in the kernels' f32 rounding order (csrc/dmip_device.h):
     c_mu = f32(1 - 0.5 lmbd), c_sig = f32(sqrt(1 - lmbd)) (double, rounded once), g_mu = fl(c_mu g),
     g_sig = fl(c_sig g), mu = fl(fl(g_mu a) - fl(fl(-0.5 beta) x)), sigma = g_sig,
     x' = fl(fl(x + fl(delta mu)) + fl(fl(sqrt(delta) g_sig) xi))."""
     F = np.float32
     x, a, xi = (np.asarray(v, F) for v in (x, a, xi))
-    beta = O.vp_beta(F(tau))
-    g = O.vp_g(F(tau))
+    beta = O.vp_beta(F(tau), beta_min, beta_max)
+    g = O.vp_g(F(tau), beta_min, beta_max)
     g_mu = (F(1.0 - 0.5 * lmbd) * g).astype(F)
     g_sig = (F((1.0 - lmbd) ** 0.5) * g).astype(F)
     mu = ((g_mu * a).astype(F) - ((F(-0.5) * beta).astype(F) * x).astype(F)).astype(F)

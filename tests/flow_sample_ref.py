@@ -15,16 +15,18 @@ import numpy as np
 
 import flow_ref as FR
 import heun_ref as HR
+import oracle as O
 
 F32 = np.float32
 
 
-def sample_with_logq(params, x0, y, num_steps, prior_params=None, T=1.0, dtype=np.float64, mean=0.0, std=1.0):
+def sample_with_logq(params, x0, y, num_steps, prior_params=None, T=1.0, dtype=np.float64, mean=0.0, std=1.0,
+                     beta_min=O.BETA_MIN, beta_max=O.BETA_MAX):
     """(x_S (n, d) in dtype, logq (n,) float64) from the start states x0 (n, d) under one observation y."""
     x0 = np.asarray(x0, F32)
     x = x0.astype(dtype)
     n, d = x.shape
-    tau, beta, g = HR.grid(num_steps, T, dtype)
+    tau, beta, g = HR.grid(num_steps, T, dtype, beta_min, beta_max)
     delta = dtype(T / num_steps)
     half = dtype(dtype(0.5) * delta)
     z = (x0.astype(np.float64) - np.float64(F32(mean))) / np.float64(F32(std))

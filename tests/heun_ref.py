@@ -31,14 +31,15 @@ def mlp(params, inp, dtype=np.float64, act="tanh"):
     return h
 
 
-def grid(num_steps, T=1.0, dtype=np.float64):
+def grid(num_steps, T=1.0, dtype=np.float64, beta_min=O.BETA_MIN, beta_max=O.BETA_MAX):
     """tau_i, beta_i, g_i for i = 0..S: tau is the kernels' f32 grid; beta and g in the f32 rounding order of
-    step_coef (dtype float32) or in f64 from that tau."""
+    step_coef (dtype float32: bmin and bdiff = beta_max - beta_min, taken in double, each rounded to f32 once) or in
+    f64 from that tau."""
     _, tau = O.schedule(num_steps, T)
     if dtype == np.float32:
-        return tau, O.vp_beta(tau), O.vp_g(tau)
+        return tau, O.vp_beta(tau, beta_min, beta_max), O.vp_g(tau, beta_min, beta_max)
     tau = tau.astype(np.float64)
-    beta = O.BETA_MIN + (O.BETA_MAX - O.BETA_MIN) * tau
+    beta = beta_min + (beta_max - beta_min) * tau
     return tau, beta, np.sqrt(beta)
 
 
@@ -61,11 +62,12 @@ def _slope(x, a, beta, g, dtype):
     return 0.5 * g * a + 0.5 * beta * x
 
 
-def heun_sample(params, x0, y, num_steps, prior_params=None, T=1.0, dtype=np.float64, snapshot_every=0, act="tanh"):
+def heun_sample(params, x0, y, num_steps, prior_params=None, T=1.0, dtype=np.float64, snapshot_every=0, act="tanh",
+                beta_min=O.BETA_MIN, beta_max=O.BETA_MAX):
     """x_S (n, d) from x0 (n, d) under one observation y; with snapshot_every > 0 also the states after every
     snapshot_every-th full step, (S // snapshot_every, n, d)."""
     x = np.asarray(x0, dtype).copy()
-    tau, beta, g = grid(num_steps, T, dtype)
+    tau, beta, g = grid(num_steps, T, dtype, beta_min, beta_max)
     delta = dtype(T / num_steps)
     half = dtype(dtype(0.5) * delta)
     snaps = []
@@ -81,10 +83,11 @@ def heun_sample(params, x0, y, num_steps, prior_params=None, T=1.0, dtype=np.flo
     return (x, np.stack(snaps)) if snapshot_every else x
 
 
-def euler_sample(params, x0, y, num_steps, prior_params=None, T=1.0, act="tanh"):
+def euler_sample(params, x0, y, num_steps, prior_params=None, T=1.0, act="tanh", beta_min=O.BETA_MIN,
+                 beta_max=O.BETA_MAX):
     """The lmbd = 1 Euler sampler in f64 (flow_ref.ode_sample without the Jacobians)."""
     x = np.asarray(x0, np.float64).copy()
-    tau, beta, g = grid(num_steps, T)
+    tau, beta, g = grid(num_steps, T, beta_min=beta_min, beta_max=beta_max)
     delta = T / num_steps
     for i in range(num_steps):
         a = score(params, x, y, tau[i], g[i], prior_params, np.float64, act)
