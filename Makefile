@@ -10,8 +10,9 @@ X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o \
           $(CSRC)/dmip_x3_flow.o $(CSRC)/dmip_x3_flow_cde.o $(CSRC)/dmip_x3_flow_post.o \
           $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o
-# the C-ABI layer by concern: packers and handles, sampling entry points, training entry points
-CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train
+# the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, training entry points) and
+# the weight packers (pure host code, dmip_pack.h)
+CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train dmip_pack
 CAPIOBJS := $(patsubst %,$(CSRC)/%.o,$(CAPI))
 OBJS := $(CSRC)/dmip_kernels.o $(CSRC)/dmip_train.o $(CSRC)/dmip_eval.o $(CSRC)/dmip_surrogate.o $(CSRC)/dmip_gemm.o $(CSRC)/dmip_jets.o $(CSRC)/dmip_step.o $(F32OBJS) $(X3OBJS) $(CAPIOBJS)
 HDRS := $(CSRC)/dmip_device.h $(CSRC)/dmip_internal.h include/dmip.h
@@ -80,7 +81,8 @@ $(CSRC)/dmip_x3k.o: $(CSRC)/dmip_x3k.hip $(CSRC)/dmip_x3k.h $(CSRC)/dmip_x3.h $(
 $(CSRC)/dmip_dps_x3.o: $(CSRC)/dmip_dps_x3.hip $(CSRC)/dmip_mh_chains.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-$(CSRC)/dmip_capi_%.o: $(CSRC)/dmip_capi_%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)
+CAPIHDRS := $(CSRC)/dmip_capi_common.h $(CSRC)/dmip_pack.h $(HDRS)
+$(CAPIOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp $(CAPIHDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(PKG)/libdmip.so: $(OBJS)
@@ -93,7 +95,7 @@ $(PKG)/libdmip.so: $(OBJS)
 # per-chunk stamps (scripts/x3p_stamps.py) replace its snapshots, so they need their own build:
 # make diag X3P_DIAG=-DDMIP_X3P_DIAG
 DIAG_DIR := abv/diag
-DIAG_SRCS := dmip_x3_cde dmip_x3k dmip_capi_pack dmip_capi_sample
+DIAG_SRCS := dmip_x3_cde dmip_x3k dmip_capi_pack dmip_capi_sample dmip_pack
 diag: $(DIAG_DIR)/libdmip_diag.so
 $(DIAG_DIR)/%_diag.o: $(CSRC)/%.hip $(CSRC)/dmip_x3k.h $(CSRC)/dmip_x3.h $(CSRC)/dmip_x3s.h $(HDRS)
 	@mkdir -p $(DIAG_DIR)
@@ -102,8 +104,8 @@ X3P_DIAG ?=
 $(DIAG_DIR)/dmip_x3p_diag.o: $(CSRC)/dmip_x3p.hip $(CSRC)/dmip_x3p.h $(CSRC)/dmip_x3.h $(HDRS)
 	@mkdir -p $(DIAG_DIR)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize $(X3P_DIAG) -c $< -o $@
-# the paired engine's packer (dmip_capi_pack.cpp) and its launch (dmip_capi_sample.cpp)
-$(DIAG_DIR)/dmip_capi_%_diag.o: $(CSRC)/dmip_capi_%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)
+# the paired engine's packer (dmip_pack.cpp), its upload (dmip_capi_pack.cpp) and its launch (dmip_capi_sample.cpp)
+$(DIAG_DIR)/%_diag.o: $(CSRC)/%.cpp $(CAPIHDRS)
 	@mkdir -p $(DIAG_DIR)
 	$(HIPCC) $(HIPFLAGS) -DDMIP_WITH_X3P -c $< -o $@
 $(DIAG_DIR)/libdmip_diag.so: $(filter-out $(patsubst %,$(CSRC)/%.o,$(DIAG_SRCS)),$(OBJS)) $(patsubst %,$(DIAG_DIR)/%_diag.o,$(DIAG_SRCS)) $(DIAG_DIR)/dmip_x3p_diag.o
@@ -122,17 +124,34 @@ scripts/ubench/%: scripts/ubench/%.hip
 ASAN_DIR := build/asan
 HOSTCXX ?= /opt/rocm/lib/llvm/bin/clang++
 ASANFLAGS := -O1 -g -std=c++17 -fPIC -fsanitize=address -fno-omit-frame-pointer
-asan: $(ASAN_DIR)/capi_args
-$(ASAN_DIR)/%_asan.o: $(CSRC)/%.cpp $(CSRC)/dmip_capi_common.h $(HDRS)
+HOSTINC := -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
+# the packers' program (tests/pack/pack_images.cpp, below) joins where a tree carries it; capi_args needs no more than
+# tests/asan/capi_args.cpp, as before
+asan: $(ASAN_DIR)/capi_args $(if $(wildcard tests/pack/pack_images.cpp),$(ASAN_DIR)/pack_images)
+$(ASAN_DIR)/%_asan.o: $(CSRC)/%.cpp $(CAPIHDRS)
 	@mkdir -p $(ASAN_DIR)
-	$(HOSTCXX) -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $(ASANFLAGS) -c $< -o $@
+	$(HOSTCXX) -x c++ $(HOSTINC) $(ASANFLAGS) -c $< -o $@
 $(ASAN_DIR)/libdmip_asan.so: $(filter-out $(CAPIOBJS),$(OBJS)) $(patsubst %,$(ASAN_DIR)/%_asan.o,$(CAPI))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -fsanitize=address $^ -o $@
 $(ASAN_DIR)/capi_args: tests/asan/capi_args.cpp $(ASAN_DIR)/libdmip_asan.so include/dmip.h
 	$(HOSTCXX) $(ASANFLAGS) $< -L$(ASAN_DIR) -ldmip_asan -Wl,-rpath,$(abspath $(ASAN_DIR)) -lpthread -o $@
 
+# The packers without a GPU (tests/test_pack_images.py, tests/golden/pack_images.md): tests/pack/pack_images.cpp prints
+# a hash of every image dmip_pack.cpp makes of a few small networks. Compiled with the paired engine's packer; linked
+# with the library for the kernels' layout constants. `make asan` builds the same program under AddressSanitizer.
+PACK_DIR := build/pack
+PACKSRCS := tests/pack/pack_images.cpp $(CSRC)/dmip_pack.cpp
+PACKFLAGS := $(HOSTINC) -std=c++17 -ffp-contract=off -DDMIP_WITH_X3P
+packcheck: $(PACK_DIR)/pack_images
+	@$<
+$(PACK_DIR)/pack_images: $(PACKSRCS) $(CAPIHDRS) $(PKG)/libdmip.so
+	@mkdir -p $(PACK_DIR)
+	$(HOSTCXX) $(PACKFLAGS) -O3 $(PACKSRCS) -L$(PKG) -ldmip -Wl,-rpath,$(abspath $(PKG)) -lpthread -o $@
+$(ASAN_DIR)/pack_images: $(PACKSRCS) $(CAPIHDRS) $(ASAN_DIR)/libdmip_asan.so
+	$(HOSTCXX) $(PACKFLAGS) $(ASANFLAGS) $(PACKSRCS) -L$(ASAN_DIR) -ldmip_asan -Wl,-rpath,$(abspath $(ASAN_DIR)) -lpthread -o $@
+
 clean:
 	rm -f $(OBJS) $(PKG)/libdmip.so $(UBENCH)
-	rm -rf $(ASAN_DIR)
+	rm -rf $(ASAN_DIR) $(PACK_DIR)
 
-.PHONY: all clean ubench asan diag
+.PHONY: all clean ubench asan diag packcheck

@@ -14,83 +14,78 @@
 
 #include "../../include/dmip.h"
 #include "dmip_internal.h"
+#include "dmip_pack.h"
 
+// A device buffer a handle owns: freed with the handle, read as a plain pointer
+struct DevMem {
+  void* ptr = nullptr;
+  DevMem() = default;
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  ~DevMem() {
+    if (ptr) (void)hipFree(ptr);
+  }
+};
+template <typename T>
+struct DevBuf : DevMem {
+  operator T*() const { return (T*)ptr; }
+};
+
+// Every device buffer is the upload of the image of the same name in dmip_pack.h (dmip_mlp_create)
 struct dmip_mlp {
   int in_dim = 0, out_dim = 0, n_hidden = 0, width = 0, act_mode = 0, layout = 0, xdim = 0;
   int k1s_full = 0;
-  char* hidden = nullptr;         // [(L-1)][W/32][W/16] KiB
-  char* ao_samp = nullptr;        // [W/16] KiB, output rows duplicated into lanes 32-63
-  char* ao_full = nullptr;        // [W/16] KiB, natural output rows
-  float* bias_hidden = nullptr;   // [(L-1)][W/32][2][16]
-  float* bias_out_samp = nullptr; // [2][16]
-  float* bias_out_full = nullptr; // [2][16]
-  char* a1_full = nullptr;        // [W/32][k1s_full] KiB (every input column varying)
-  char* ring_l1 = nullptr;        // width 512: [layer-1 chunks (split image) | hidden | output] (CDiffE sampler)
-  float* w1 = nullptr;            // layer-1 fp32 [W][in_dim] (per-y prep of the sampler's A1)
-  float* b1 = nullptr;
+  DevBuf<char> hidden;          // [(L-1)][W/32][W/16] KiB | ao_samp
+  DevBuf<char> ao_samp;         // [W/16] KiB, output rows duplicated into lanes 32-63
+  DevBuf<char> ao_full;         // [W/16] KiB, natural output rows
+  DevBuf<float> bias_hidden;    // [(L-1)][W/32][2][16]
+  DevBuf<float> bias_out_samp;  // [2][16]
+  DevBuf<float> bias_out_full;  // [2][16]
+  DevBuf<char> a1_full;         // [W/32][k1s_full] KiB (every input column varying)
+  DevBuf<char> ring_l1;         // width 512: [layer-1 chunks (split image) | hidden | output] (CDiffE sampler)
+  DevBuf<float> w1, b1;         // layer-1 fp32 [W][in_dim], [W] (per-y prep of the sampler's A1)
   // exact-f32 images of a DPS prior (MLP2 (x, t), x 3, widths [256]*3): dmip_dps_sample
-  float* dps_l1 = nullptr;        // [16 tiles][2 k-steps][64]
-  char* dps_w2 = nullptr;         // [16][16][64][4]
-  char* dps_w3 = nullptr;
-  char* dps_w4 = nullptr;         // [1][16][64][4], rows >= 3 zero
-  float* dps_bias = nullptr;      // b2 | b3 | b4[16]
+  DevBuf<float> dps_l1;         // [16 tiles][2 k-steps][64]
+  DevBuf<char> dps_w2, dps_w3;  // [16][16][64][4]
+  DevBuf<char> dps_w4;          // [1][16][64][4], rows >= 3 zero
+  DevBuf<float> dps_bias;       // b2 | b3 | b4[16]
   // fp32x3 images of a DPS prior (dmip_dps_x3.hip): the chunk stream, layer 1, the biases; none when a weight is
   // beyond fp16's range (dps_x3_range: that magnitude)
-  char* dps_x3_img = nullptr;     // [kDpsX3PriorChunks][32 KiB]
-  char* dps_x3_l1 = nullptr;      // [16 tiles][64][8] fp16, scaled by 2 log2 e
-  float* dps_x3_bias = nullptr;   // c b1 | init2 | init3 [256] | out init [16]
+  DevBuf<char> dps_x3_img;      // [kDpsX3PriorChunks][32 KiB]
+  DevBuf<char> dps_x3_l1;       // [16 tiles][64][8] fp16, scaled by 2 log2 e
+  DevBuf<float> dps_x3_bias;    // c b1 | init2 | init3 [256] | out init [16]
   double dps_x3_range = 0.0;
   // exact-f32 images (DMIP_PREC_F32, dmip_f32.h): every input column + bias as layer 1
-  float* f32_l1 = nullptr;        // [W/16][k1q][64]
-  char* f32_stream = nullptr;     // [(L-1) W/16 + f32_ot chunks][W/16][64][4]
-  float* f32_bias = nullptr;      // [(L-1)][W] | [16 f32_ot]
+  DevBuf<float> f32_l1;         // [W/16][k1q][64]
+  DevBuf<char> f32_stream;      // [(L-1) W/16 + f32_ot chunks][W/16][64][4]
+  DevBuf<float> f32_bias;       // [(L-1)][W] | [16 f32_ot]
   int f32_k1q = 0, f32_ot = 0;
   // fp32-accurate split-fp16 images (DMIP_PREC_F32X3, dmip_x3.h); none when a scaled weight or folded bias
   // is outside fp16's range (x3_range: that magnitude, reported by em_sample_x3)
   double x3_range = 0.0;
-  char* x3_l1 = nullptr;          // [W/16][K1Q][64][8] fp16 over (x, t)
-  char* x3_l1_full = nullptr;     // the same over every input column (X_Y_T networks: CDiffE)
-  char* x3_stream = nullptr;      // hidden chunks | output chunk
-  char* x3_stream_l1r = nullptr;  // CDiffE at width 512: layer-1 chunks ([K1Q][W/16 tiles][64][8]) | x3_stream
-  float* x3_bias = nullptr;       // [L W + 16]
+  DevBuf<char> x3_l1;           // [W/16][K1Q][64][8] fp16 over (x, t)
+  DevBuf<char> x3_l1_full;      // the same over every input column (X_Y_T networks: CDiffE)
+  DevBuf<char> x3_stream;       // hidden chunks | output chunk
+  DevBuf<char> x3_stream_l1r;   // CDiffE at width 512: layer-1 chunks ([K1Q][W/16 tiles][64][8]) | x3_stream
+  DevBuf<float> x3_bias;        // [L W + 16]
   // the k-major engine's images (dmip_x3k.h; width 256, 3 hidden layers, xdim <= 4)
-  char* x3k_stream = nullptr;     // [2 layers][8 k-steps][16 tiles][hi, lo][64][8] fp16
-  char* x3k_out = nullptr;        // [8 k-steps][64][8]: rows 0..xdim-1 W_hi, rows 4..4+xdim-1 W_lo
+  DevBuf<char> x3k_stream;      // [2 layers][8 k-steps][16 tiles][hi, lo][64][8] fp16
+  DevBuf<char> x3k_out;         // [8 k-steps][64][8]: rows 0..xdim-1 W_hi, rows 4..4+xdim-1 W_lo
   // the paired-tile 32x32 engine's images (dmip_x3p.h; same shapes)
-  char* x3p_stream = nullptr;     // [16 chunks][32 KiB]
-  char* x3p_l1 = nullptr;         // [8 layer-1 tiles][64][8] | [2 hidden layers][8 bias tiles][64][8] fp16
-  float* x3p_ow = nullptr;        // f32 output rows [8][2][4][4][4] | init[16]
-  ~dmip_mlp() {
-    for (void* p : {(void*)ring_l1, (void*)hidden, (void*)ao_samp, (void*)ao_full, (void*)bias_hidden, (void*)bias_out_samp,
-                    (void*)bias_out_full, (void*)a1_full, (void*)w1, (void*)b1, (void*)dps_l1, (void*)dps_w2,
-                    (void*)dps_w3, (void*)dps_w4, (void*)dps_bias, (void*)f32_l1, (void*)f32_stream,
-                    (void*)f32_bias, (void*)x3_l1, (void*)x3_l1_full, (void*)x3_stream, (void*)x3_stream_l1r,
-                    (void*)x3_bias,
-                    (void*)x3k_stream, (void*)x3k_out, (void*)x3p_stream, (void*)x3p_l1, (void*)x3p_ow,
-                    (void*)dps_x3_img, (void*)dps_x3_l1, (void*)dps_x3_bias})
-      if (p) (void)hipFree(p);
-  }
+  DevBuf<char> x3p_stream;      // [16 chunks][32 KiB]
+  DevBuf<char> x3p_l1;          // [8 layer-1 tiles][64][8] | [2 hidden layers][8 bias tiles][64][8] fp16
+  DevBuf<float> x3p_ow;         // f32 output rows [8][2][4][4][4] | init[16]
 };
 
 // the scatterometry surrogate
 struct dmip_surrogate {
-  float* l1 = nullptr;
-  float* bias = nullptr;
-  char* img[7] = {};  // w2, w3, w4, w3t, w2t, w4t, w1t
+  DevBuf<float> l1, bias;
+  DevBuf<char> img[7];  // w2, w3, w4, w3t, w2t, w4t, w1t
   // fp32x3 images (dmip_dps_x3.hip): chunks S2 | S3 | Sout | S4^T | S3^T | S2^T | S1^T, layer 1, biases; none when
   // a weight is beyond fp16's range (x3_range)
-  char* x3_img = nullptr;
-  char* x3_l1 = nullptr;
-  float* x3_bias = nullptr;  // b1 | b2 | b3 [256] | b4 [32]
+  DevBuf<char> x3_img, x3_l1;
+  DevBuf<float> x3_bias;  // b1 | b2 | b3 [256] | b4 [32]
   double x3_range = 0.0;
-  ~dmip_surrogate() {
-    if (l1) (void)hipFree(l1);
-    if (bias) (void)hipFree(bias);
-    for (char* p : img)
-      if (p) (void)hipFree(p);
-    for (void* p : {(void*)x3_img, (void*)x3_l1, (void*)x3_bias})
-      if (p) (void)hipFree(p);
-  }
 };
 
 namespace dmip_capi {
@@ -108,18 +103,7 @@ inline int hip_fail(hipError_t e, const char* what) {
   return fail(DMIP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-inline int k1s_for(int n_slots) { return (n_slots + 15) / 16; }
-
-template <typename T>
-int upload(T** dst, const std::vector<T>& src) {
-  *dst = nullptr;
-  if (src.empty()) return DMIP_OK;
-  hipError_t e = hipMalloc((void**)dst, src.size() * sizeof(T));
-  if (e != hipSuccess) return fail(DMIP_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
-  e = hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
-  return DMIP_OK;
-}
+using dmip_pack::k1s_for;
 
 // Scratch of one launch sequence, allocated on its stream and freed on it when the owner leaves scope: the free is
 // enqueued behind whatever the entry point launched, on every return path.

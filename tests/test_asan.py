@@ -1,13 +1,16 @@
 """Host-side AddressSanitizer run of the C-ABI layer (SURVEY.md §5 "Race detection / sanitizers"):
 `make asan` builds the dmip_capi_*.cpp sources with -fsanitize=address (host code only; GPU sanitizers are not
 available on this pool), links it with the regular kernel objects, and tests/asan/capi_args.cpp drives
-every entry point's argument validation and the thread-local error buffer. CPU only."""
+every entry point's argument validation and the thread-local error buffer. The packers sit behind no upload
+(csrc/dmip_pack.cpp is pure host code), so the same build runs them too: tests/pack/pack_images.cpp packs every
+image of its small networks under ASan and must print the hashes of tests/golden/pack_images.json. CPU only."""
 import os
 import subprocess
 
 import pytest
 
 from conftest import ROOT
+from test_pack_images import check
 
 OBJ = os.path.join(ROOT, "diffusion-modelling-for-inverse-problems_amd", "csrc", "dmip_kernels.o")
 
@@ -23,3 +26,16 @@ def test_capi_argument_validation_under_asan():
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert "ok: 0 failure(s)" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr
+
+
+def test_packers_under_asan():
+    if not os.path.exists(OBJ):
+        pytest.skip("kernel objects not built (make)")
+    r = subprocess.run(["make", "-C", ROOT, "asan"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
+    r = subprocess.run([os.path.join(ROOT, "build", "asan", "pack_images")], capture_output=True, text=True,
+                       timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr
+    check(r.stdout)
