@@ -85,6 +85,26 @@ static_assert(KLay::TOTAL <= 160 * 1024, "LDS budget");
 
 typedef __attribute__((address_space(3))) void lds_void;
 
+// The ring's A fragments are written by ds_read_b128 and read by MFMAs only, and both address AGPRs: read into
+// the accumulator file (AG: x3::lds_rd and x3::lds_wait2 with "a" operands), they leave the ArchVGPRs to the values
+// the vector ALUs work on (layer 1's pre-activations above all, which the VGPR-form MFMA of l1_tile keeps there).
+// AG = false (one chain tile per wave: two waves per SIMD, every MFMA in the VGPR form) is x3::lds_rd itself.
+template <int OFF, bool AG>
+__device__ __forceinline__ u32x4 ring_rd(x3::lds_cptr p) {
+  if constexpr (AG) {
+    u32x4 r;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(r) : "v"(p), "i"(OFF));
+    return r;
+  } else {
+    return x3::lds_rd<OFF>(p);
+  }
+}
+template <int N, bool AG>
+__device__ __forceinline__ void ring_wait2(u32x4& a, u32x4& b) {
+  if constexpr (AG) asm volatile("s_waitcnt lgkmcnt(%2)" : "+a"(a), "+a"(b) : "i"(N));
+  else x3::lds_wait2<N>(a, b);
+}
+
 // diagnostic phase stamps (DIAG & 2 only, never in a product kernel): the shader cycle counter, read in an
 // asm statement so that no code moves across it
 __device__ __forceinline__ uint64_t stamp() {
@@ -115,6 +135,7 @@ __device__ __forceinline__ void act_kstep(const f32x4& z0, const f32x4& z1, u32x
 template <int D, int NT, bool NOISE, int DIAG>
 struct KEngine {
   static constexpr int NWV = KWaves<NT>::NWV, PPW = KWaves<NT>::PPW;
+  static constexpr bool AG = NT > 1;  // ring fragments in AGPRs (ring_rd)
   char* lds;
   const char* ring_lane;  // ring base + 16 lane
   const char* out_lane;   // resident output fragments + 16 lane
@@ -161,9 +182,9 @@ struct KEngine {
     const x3::lds_cptr b0 = (x3::lds_cptr)ring_lane;
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
-      fpre[i][0] = x3::lds_rd<0>(b0 + i * 2048);
-      fpre[i][1] = x3::lds_rd<1024>(b0 + i * 2048);
-      x3::lds_wait2<0>(fpre[i][0], fpre[i][1]);
+      fpre[i][0] = ring_rd<0, AG>(b0 + i * 2048);
+      fpre[i][1] = ring_rd<1024, AG>(b0 + i * 2048);
+      ring_wait2<0, AG>(fpre[i][0], fpre[i][1]);
     }
   }
 
@@ -223,7 +244,7 @@ struct KEngine {
       // the next chunk's first fragments (read at the last PF o-steps) are complete before they leave the
       // chunk: an asm load's registers must not be copied before its data lands
 #pragma unroll
-      for (int i = 0; i < PF; ++i) x3::lds_wait2<0>(fpre[i][0], fpre[i][1]);
+      for (int i = 0; i < PF; ++i) ring_wait2<0, AG>(fpre[i][0], fpre[i][1]);
       if constexpr (Q + 1 < KQ) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) Hh[t] = Nh[t], Hl[t] = Nl[t];
@@ -274,14 +295,14 @@ struct KEngine {
   __device__ __forceinline__ void ring_pre(x3::lds_cptr base, x3::lds_cptr nbase, u32x4 (&f)[PF + 1][2],
                                            u32x4 (&fpre)[PF][2]) const {
     if constexpr (O + PF < ST) {
-      f[(O + PF) % (PF + 1)][0] = x3::lds_rd<(O + PF) * 2048>(base);
-      f[(O + PF) % (PF + 1)][1] = x3::lds_rd<(O + PF) * 2048 + 1024>(base);
+      f[(O + PF) % (PF + 1)][0] = ring_rd<(O + PF) * 2048, AG>(base);
+      f[(O + PF) % (PF + 1)][1] = ring_rd<(O + PF) * 2048 + 1024, AG>(base);
     } else {
-      fpre[O + PF - ST][0] = x3::lds_rd<(O + PF - ST) * 2048>(nbase);
-      fpre[O + PF - ST][1] = x3::lds_rd<(O + PF - ST) * 2048 + 1024>(nbase);
+      fpre[O + PF - ST][0] = ring_rd<(O + PF - ST) * 2048, AG>(nbase);
+      fpre[O + PF - ST][1] = ring_rd<(O + PF - ST) * 2048 + 1024, AG>(nbase);
     }
     // PF younger fragment pairs are in flight (an output-fragment read between them only makes it stricter)
-    x3::lds_wait2<2 * PF>(f[O % (PF + 1)][0], f[O % (PF + 1)][1]);
+    ring_wait2<2 * PF, AG>(f[O % (PF + 1)][0], f[O % (PF + 1)][1]);
   }
   // hidden layer 1: the o-step that activates operand pair P (< 4 NT) of the next k-step -- pair P at o-step P, or
   // (DMIP_X3K_ACT_SPREAD) the 4 NT pairs spread evenly over the 16 o-steps
@@ -356,7 +377,7 @@ struct KEngine {
       for (int i = 0; i < PF; ++i) f[i][0] = fpre[i][0], f[i][1] = fpre[i][1];
       ostep2<H, Q2, 0>(base, nbase, In, Out, Ah, Al, f, fpre, oH, oL, fo, eh, el);
 #pragma unroll
-      for (int i = 0; i < PF; ++i) x3::lds_wait2<0>(fpre[i][0], fpre[i][1]);
+      for (int i = 0; i < PF; ++i) ring_wait2<0, AG>(fpre[i][0], fpre[i][1]);
       chunk2<H, Q2 + 1>(In, Out, Ah, Al, fpre, oH, oL, fo, eh, el);
     }
   }
@@ -505,6 +526,37 @@ __device__ __forceinline__ void l1_read(x3::lds_cptr la, x3::lds_cptr lb, u32x4&
   b = x3::lds_rd<O * 64>(lb);
 }
 
+// Layer 1's MFMA in the VGPR form (C and D in VGPRs): its C is the bias row that l1_read left in VGPRs, and its D is
+// read by the vector ALUs (the double tanh), which cannot address AGPRs. The builtin takes the AGPR form in a kernel
+// of this size: a v_accvgpr_write per bias dword in, a v_accvgpr_read per pre-activation out, each on the vector
+// issue port with its pads. An asm statement is opaque to the compiler's hazard recognizer, so its wait states are
+// ours: FRESH_B pads the 2 states between the vector ALUs' write of the B operand and the MFMA (tile 0 only: later
+// tiles' operands are LDS reads behind their s_waitcnt, and the same b1); l1_done pads behind the last one.
+template <bool FRESH_B>
+__device__ __forceinline__ f32x4 mfma16_l1(const u32x4& a, const u32x4& b, const f32x4& c) {
+  f32x4 d;
+  if constexpr (FRESH_B)
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
+  else
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+
+// Behind layer 1's last MFMA: the 12 wait states of an 8-pass MFMA's D before any other reader, then every tile of P
+// made opaque, so that no reader of an earlier tile is scheduled above the pad either (volatile statements keep
+// their order; the empty ones cost no instruction)
+template <int NT, int ST>
+__device__ __forceinline__ void l1_done(f32x4 (&P)[NT][ST]) {
+  static_assert(ST % 8 == 0, "eight tiles per statement");
+  asm volatile("s_nop 7\n\ts_nop 3");
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int o = 0; o < ST; o += 8)
+      asm volatile("" : "+v"(P[t][o]), "+v"(P[t][o + 1]), "+v"(P[t][o + 2]), "+v"(P[t][o + 3]), "+v"(P[t][o + 4]),
+                        "+v"(P[t][o + 5]), "+v"(P[t][o + 6]), "+v"(P[t][o + 7]));
+}
+
 // tile O of layer 1 for every chain tile (fragments of tiles O, O + 1 in flight on entry; O + 2's issued here)
 template <int O, int NT, int ST>
 __device__ __forceinline__ void l1_tile(x3::lds_cptr la, x3::lds_cptr lb, u32x4 (&fa)[3], u32x4 (&fb)[3],
@@ -515,8 +567,10 @@ __device__ __forceinline__ void l1_tile(x3::lds_cptr la, x3::lds_cptr lb, u32x4 
     x3::lds_wait2<(O + 2 < ST) ? 4 : ((O + 1 < ST) ? 2 : 0)>(fa[O % 3], fb[O % 3]);
     const f32x4 c = __builtin_bit_cast(f32x4, fb[O % 3]);
 #pragma unroll
-    for (int t = 0; t < NT; ++t) P[t][O] = mfma16(fa[O % 3], b1[t], c);
+    for (int t = 0; t < NT; ++t) P[t][O] = mfma16_l1<O == 0>(fa[O % 3], b1[t], c);
     l1_tile<O + 1>(la, lb, fa, fb, b1, P);
+  } else {
+    l1_done(P);
   }
 }
 
@@ -647,8 +701,9 @@ __global__ void __launch_bounds__(KWaves<NT>::NWV * 64, KWaves<NT>::NWV / 4) x3k
         u32x4 b1[NT];
         l1_operands(x, cf.tau, g, b1);
         // the A fragments and the per-y bias rows (the MFMAs' C input) by explicit reads two tiles ahead with
-        // counted waits: left to itself the compiler waited lgkmcnt(0) before every tile's MFMAs and routed the
-        // bias through AGPRs (then copied P back out of them, each copy behind the MFMA's full latency)
+        // counted waits: left to itself the compiler waited lgkmcnt(0) before every tile's MFMAs. The MFMAs are in
+        // the VGPR form (mfma16_l1): the bias row is their C where it was read, and P stays where the double
+        // tanh reads it
         const x3::lds_cptr la = (x3::lds_cptr)l1_lane;
         const x3::lds_cptr lb = (x3::lds_cptr)(lds + L::BIAS + 16 * g);
         u32x4 fa[3], fb[3];
