@@ -5,14 +5,15 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-parameter
 F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(CSRC)/dmip_f32_cdiffe.o $(CSRC)/dmip_flow.o \
-           $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o
+           $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o \
+           $(CSRC)/dmip_dps_linear.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o \
           $(CSRC)/dmip_x3_flow.o $(CSRC)/dmip_x3_flow_cde.o $(CSRC)/dmip_x3_flow_post.o \
-          $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o
+          $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o $(CSRC)/dmip_x3_dps_linear.o
 # the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, training entry points) and
 # the weight packers (pure host code, dmip_pack.h)
-CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train dmip_pack
+CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train dmip_capi_dps_linear dmip_pack
 CAPIOBJS := $(patsubst %,$(CSRC)/%.o,$(CAPI))
 OBJS := $(CSRC)/dmip_kernels.o $(CSRC)/dmip_train.o $(CSRC)/dmip_eval.o $(CSRC)/dmip_surrogate.o $(CSRC)/dmip_gemm.o $(CSRC)/dmip_jets.o $(CSRC)/dmip_step.o $(F32OBJS) $(X3OBJS) $(CAPIOBJS)
 HDRS := $(CSRC)/dmip_device.h $(CSRC)/dmip_internal.h include/dmip.h
@@ -57,6 +58,10 @@ $(CSRC)/dmip_flow.o: $(CSRC)/dmip_flow.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow
 $(CSRC)/dmip_flow_sample.o: $(CSRC)/dmip_flow_sample.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# guided sampling for linear problems from a prior alone (dmip_flow_rows.h dps_linear_rows), exact f32
+$(CSRC)/dmip_dps_linear.o: $(CSRC)/dmip_dps_linear.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # fp32-accurate split-fp16 engine (DMIP_PREC_F32X3): one header, four translation units; no SLP
 # vectorisation (it packs the split's f32 subtractions into v_pk_add_f32, an anti-lever beside MFMAs)
 $(CSRC)/dmip_x3.o: $(CSRC)/dmip_x3.hip $(CSRC)/dmip_x3.h $(HDRS)
@@ -71,6 +76,10 @@ $(CSRC)/dmip_x3_flow.o: $(CSRC)/dmip_x3_flow.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/dmip_x3_flow_%.o: $(CSRC)/dmip_x3_flow_%.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# the same on the fp32x3 engine (listed before nothing else matches it: an explicit rule beats dmip_x3_%.o)
+$(CSRC)/dmip_x3_dps_linear.o: $(CSRC)/dmip_x3_dps_linear.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 # the k-major multi-tile fp32x3 CDE engine (width 256): its own header

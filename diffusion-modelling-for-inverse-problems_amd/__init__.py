@@ -8,7 +8,7 @@ whole reverse-SDE loop. Import with importlib (the directory name is not an iden
     dmip = importlib.import_module("diffusion-modelling-for-inverse-problems_amd")
 """
 from . import _lib
-from .estimators import DPS, BaseClassDiffusionModel, CDE, CDiffE, PosteriorDiffusionEstimator
+from .estimators import DPS, BaseClassDiffusionModel, CDE, CDiffE, LinearDPS, PosteriorDiffusionEstimator
 from .factory import get_model_from_args
 from .losses import (ConditionalScoreFPELoss, DSM_PDELoss, DSMLoss, PINNLoss, PINNLoss2, PosteriorLoss,
                      ScoreFPELoss, batch_gradient, divergence)
@@ -19,7 +19,7 @@ from .problems import (LinearForwardProblem, ScatterometryEnergy, anneal_to_ener
 from .sdes import PluginReverseSDE, VariancePreservingSDE, sample_vp_truncated_q
 
 __all__ = [
-    "BaseClassDiffusionModel", "CDE", "CDiffE", "PosteriorDiffusionEstimator", "DPS", "get_model_from_args",
+    "BaseClassDiffusionModel", "CDE", "CDiffE", "PosteriorDiffusionEstimator", "DPS", "LinearDPS", "get_model_from_args",
     "ConditionalScoreFPELoss", "DSM_PDELoss", "DSMLoss", "PINNLoss", "PINNLoss2", "PosteriorLoss",
     "ScoreFPELoss", "batch_gradient", "divergence", "MLP", "MLP2", "PosteriorScore",
     "PluginReverseSDE", "VariancePreservingSDE", "sample_vp_truncated_q", "LinearForwardProblem",

@@ -43,11 +43,12 @@ EXPORTED = (
     "dmip_dps_sample_ex", "dmip_mh_sample_ex", "dmip_em_sample_lmbd", "dmip_flow_logp", "dmip_flow_logp_supported",
     "dmip_ode_sample", "dmip_ode_sample_supported", "dmip_flow_sample", "dmip_flow_sample_supported",
     "dmip_flow_logp_ex", "dmip_flow_sample_ex", "dmip_flow_logp_supported_precision",
-    "dmip_flow_sample_supported_precision", "dmip_mala_sample",
+    "dmip_flow_sample_supported_precision", "dmip_mala_sample", "dmip_dps_linear_supported", "dmip_dps_linear_sample",
 )
 DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
 SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
 DMIP_DPS_NLL, DMIP_DPS_NORM = 0, 1
+DMIP_DPS_STEP_BETA, DMIP_DPS_STEP_NORM = 0, 1
 
 
 class DmipVpsde(ctypes.Structure):
@@ -190,6 +191,11 @@ def _declare(lib):
         lib.dmip_mala_sample.argtypes = [_c_void_p, ctypes.POINTER(DmipScatNoise), _c_void_p, _i32, _i64, _i64, _i32,
                                          _i32, ctypes.c_double, ctypes.c_double, _u64t, _c_void_p, _c_void_p,
                                          _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
+    if hasattr(lib, "dmip_dps_linear_sample"):  # additive within ABI 9
+        lib.dmip_dps_linear_supported.argtypes = [_i32] * 5
+        lib.dmip_dps_linear_sample.argtypes = [_c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p, _i32,
+                                               _c_void_p, _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _i32, _f32,
+                                               _i32, _c_void_p, _c_void_p]
     for name in EXPORTED:  # every entry point returns int but dmip_last_error
         if name != "dmip_last_error" and hasattr(lib, name):
             getattr(lib, name).restype = _i32
@@ -617,6 +623,23 @@ def dps_sample(prior, surrogate, noise, sde, y, n_chains, chain_offset, num_step
                                    int(y.shape[0]), int(n_chains), int(chain_offset), int(num_steps), float(mean),
                                    float(std), _u64(seed), int(mode), float(zeta), precision_code(precision), ptr(out),
                                    stream_of(y.device)))
+
+
+def dps_linear_supported(width, n_hidden, xdim, ydim, precision="fp32x3"):
+    return bool(lib().dmip_dps_linear_supported(width, n_hidden, xdim, ydim, precision_code(precision)))
+
+
+def dps_linear_sample(prior, sde, A, B, yres, n_chains, chain_offset, num_steps, mean, std, seed, step_rule, zeta, out,
+                      precision="fp32x3"):
+    """dmip_dps_linear_sample: guided posterior samples of a linear-Gaussian problem from the prior (x, t) network
+    alone into out (n_y, n_chains, xdim). A (ydim, xdim), B (n_B, ydim, xdim) the guidance table, yres (n_y, ydim)
+    = y - b: contiguous f32 device tensors. "fp32" the exact-f32 kernel, any other precision the fp32x3 one."""
+    calls["dps_linear_sample"] += 1
+    _status_pending.add(_dev_index(yres.device))
+    check(lib().dmip_dps_linear_sample(prior.h, ctypes.byref(sde), ptr(A), ptr(B), int(B.shape[0]), ptr(yres),
+                                       int(yres.shape[1]), int(yres.shape[0]), int(n_chains), int(chain_offset),
+                                       int(num_steps), float(mean), float(std), _u64(seed), int(step_rule),
+                                       float(zeta), precision_code(precision), ptr(out), stream_of(yres.device)))
 
 
 def posterior_loss_grad(prior_layers, lik_layers, surrogate, noise, lam, sde, x, y, t, eps, grad_prior, grad_lik,

@@ -1,0 +1,91 @@
+// libdmip.so C-ABI, guided posterior sampling for a linear-Gaussian problem from a prior score network alone
+// (dmip_dps_linear.hip, dmip_x3_dps_linear.hip). Argument validation first, then one stream-ordered launch.
+#include "dmip_capi_common.h"
+
+using namespace dmip_capi;
+
+extern "C" {
+
+// the tanh chain's answer (a SiLU prior is refused by the entry point); DMIP_PREC_FP16 runs the fp32x3 kernel, as
+// the flow entry points
+int dmip_dps_linear_supported(int width, int n_hidden, int xdim, int ydim, int precision) {
+  if (precision != DMIP_PREC_F32 && precision != DMIP_PREC_F32X3 && precision != DMIP_PREC_FP16) return 0;
+  return dmip::dps_linear_supported(width, n_hidden, xdim, ydim) ? 1 : 0;
+}
+
+// every argument is validated before any device work
+int dmip_dps_linear_sample(const dmip_mlp* prior, const dmip_vpsde* sde, const float* A_dev, const float* B_dev, int n_B,
+                           const float* yres_dev, int ydim, int n_y, int64_t n_chains, int64_t chain_offset,
+                           int num_steps, float mean, float stdv, uint64_t seed, int step_rule, float zeta,
+                           int precision, float* x_out_dev, void* stream) {
+  if (!prior || !sde || !A_dev || !B_dev || !yres_dev || !x_out_dev) return fail(DMIP_ERR_INVALID, "null argument");
+  if (step_rule != DMIP_DPS_STEP_BETA && step_rule != DMIP_DPS_STEP_NORM)
+    return fail(DMIP_ERR_INVALID, "unknown dps_linear step rule");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (n_B != 1 && n_B != num_steps) return fail(DMIP_ERR_INVALID, "n_B must be 1 or num_steps");
+  if (ydim < 1 || ydim > dmip::kDpsLinearMaxY) return fail(DMIP_ERR_INVALID, "ydim must be in [1, 32]");
+  if (!(zeta >= 0.0f) || !std::isfinite(zeta)) return fail(DMIP_ERR_INVALID, "zeta must be finite and >= 0");
+  if (n_y < 1 || n_y > 65535) return fail(DMIP_ERR_INVALID, "n_y must be in [1, 65535]");
+  if (n_chains < 0 || chain_offset < 0) return fail(DMIP_ERR_INVALID, "negative chain count/offset");
+  if (!(sde->T > 0.0)) return fail(DMIP_ERR_INVALID, "T must be > 0");
+  if (prior->layout != DMIP_INPUT_X_T || prior->out_dim != prior->xdim || prior->in_dim != prior->xdim + 1)
+    return fail(DMIP_ERR_INVALID, "dps_linear prior must be an x,t network with out_dim == xdim");
+  if (f32_act(prior)) return fail(DMIP_ERR_UNSUPPORTED, "dps_linear: the tanh chain only (no SiLU kernel)");
+  if (precision != DMIP_PREC_F32 && precision != DMIP_PREC_F32X3 && precision != DMIP_PREC_FP16)
+    return fail(DMIP_ERR_UNSUPPORTED, "dps_linear: no kernel for this precision (DMIP_PREC_F32 or DMIP_PREC_F32X3)");
+  const bool x3 = precision != DMIP_PREC_F32;
+  const int xdim = prior->xdim;
+  if (!dmip::dps_linear_supported(prior->width, prior->n_hidden, xdim, ydim))
+    return fail(DMIP_ERR_UNSUPPORTED, "no compiled dps_linear kernel for width " + std::to_string(prior->width) +
+                                          ", layers " + std::to_string(prior->n_hidden) + ", xdim " +
+                                          std::to_string(xdim));
+  if (x3 && prior->x3_range > 0.0)
+    return fail(DMIP_ERR_UNSUPPORTED,
+                "dps_linear (fp32x3): a weight is outside the fp16 range of the split engine (largest scaled |w| " +
+                    std::to_string(prior->x3_range) + " > 65504); use DMIP_PREC_F32");
+  if (x3 ? !prior->x3_stream : (!prior->f32_l1 || prior->f32_k1q != (xdim + 2 + 3) / 4))
+    return fail(DMIP_ERR_UNSUPPORTED, "dps_linear: the prior has no image for this precision");
+  if (n_chains == 0) return DMIP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  dmip::DpsLinearChains c{};
+  c.A = A_dev;
+  c.B = B_dev;
+  c.yres = yres_dev;
+  c.x_out = x_out_dev;
+  c.n = n_chains;
+  c.chain_offset = chain_offset;
+  c.num_steps = num_steps;
+  c.ydim = ydim;
+  c.n_B = n_B;
+  c.step_rule = step_rule;
+  c.T = (float)sde->T;
+  c.bmin = (float)sde->beta_min;
+  c.bdiff = (float)(sde->beta_max - sde->beta_min);
+  c.delta = (float)(sde->T / (double)num_steps);
+  c.sqrt_delta = (float)std::sqrt(sde->T / (double)num_steps);
+  c.mean = mean;
+  c.stdv = stdv;
+  c.zeta = zeta;
+  c.seed = seed;
+  bool ok = false;
+  hipError_t e;
+  if (x3) {
+    dmip::X3DpsLinearParams p{};
+    p.net = dmip::X3Net{prior->x3_l1, prior->x3_stream, prior->x3_bias};
+    p.n_hidden = prior->n_hidden;
+    p.chains = c;
+    p.err = status_word(dmip::stream_device(st));
+    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+    e = dmip::launch_x3_dps_linear(p, prior->width, xdim, n_y, st, &ok);
+  } else {
+    dmip::F32DpsLinearParams p{};
+    p.net = f32_net(prior);
+    p.n_hidden = prior->n_hidden;
+    p.chains = c;
+    e = dmip::launch_f32_dps_linear(p, prior->width, xdim, n_y, st, &ok);
+  }
+  if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled dps_linear kernel");
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "dps_linear launch");
+}
+
+}  // extern "C"

@@ -100,6 +100,29 @@ __device__ __forceinline__ void flow_score(typename C::E& eng, const int& g, con
   flow::gather_score<MODE, D>(out, j, cf, a, dv);
 }
 
+// flow_score's network half for a one-network configuration, the output tile itself: rows 4 g + r of net 0 over the
+// 16 columns (s_k of the primal columns, ds_k/dx_{m-1} of the tangent columns, at g = 0), for a caller that keeps every
+// tangent entry (flow::gather_jac; dmip_dps_linear.hip)
+template <typename C, int D, typename Coef>
+__device__ __forceinline__ f32x4 flow_out(typename C::E& eng, const int& g, const int& m, const float (&xin)[D],
+                                          const Coef& cf) {
+  using L = typename C::L;
+  using E = typename C::E;
+  static_assert(C::NNET == 1, "one network");
+  float v[D + 1];
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = xin[k];
+  v[D] = cf.tau;
+  float b0[C::K1Q0];
+  l1_operand<D + 1, C::K1Q0>(v, g, b0);
+#pragma unroll
+  for (int s = 0; s < C::K1Q0; ++s) {
+    const float e = (4 * s + g == m - 1 && m - 1 < D) ? 1.0f : 0.0f;
+    b0[s] = m == 0 ? b0[s] : e;
+  }
+  return flow_eval<E, C::K1Q0>(eng, 0, L::L1_0, b0, m);
+}
+
 // the flow kernels' set-up: layer-1 images (net 0's is the per-y one) and biases into LDS, ring started
 // (f32_flow_kernel calls it; f32_flow_sample_kernel carries the same text, dmip_flow_sample.hip says why)
 template <typename C, int W>

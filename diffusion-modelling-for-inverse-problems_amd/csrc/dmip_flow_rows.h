@@ -209,6 +209,110 @@ __device__ __forceinline__ void sample_rows(const FlowChains& p, Rows<NW>& rows,
   }
 }
 
+// ---------------------------------------------------------------------------- guided sampling, linear problems
+// gather_score's sibling that keeps every tangent entry: s_k of the row on all its lanes and J[k][n] = ds_k/dx_n (the
+// tangent column 1 + n carries d/dx_n of every output row k)
+template <int D, typename V>
+__device__ __forceinline__ void gather_jac(const V& out, const int& j, float (&s)[D], float (&J)[D][D]) {
+  const int q0 = j & 12;  // the row's primal column, at g = 0
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    s[k] = __shfl(out[k], q0, 64);
+#pragma unroll
+    for (int n = 0; n < D; ++n) J[k][n] = __shfl(out[k], q0 + 1 + n, 64);
+  }
+}
+
+// var(t) = 1 - exp(-0.5 t^2 (bmax - bmin) - t bmin) in the reference's evaluation order (sdes.py:27-28), beside
+// dmip_device.h's vp_mean_weight
+__device__ __forceinline__ float vp_var(float t, float bmin, float bdiff) {
+  const float a = __fmul_rn(__fmul_rn(-0.5f, __fmul_rn(t, t)), bdiff);
+  return __fsub_rn(1.0f, expf(__fsub_rn(a, __fmul_rn(t, bmin))));
+}
+
+// Posterior samples of y = A x + b + eta, eta ~ N(0, Sigma), from a prior score network s(x, tau) alone. Reverse grid
+// of the samplers at lmbd = 0: tau_i, beta_i, g_i = step_coef(i, S, ...), alpha_i = vp_mean_weight(tau_i), v_i =
+// vp_var(tau_i), delta = T / S. A chain starts at x = mean + std n (the first normals of its stream (seed,
+// chain_offset + row, y index), as every sampler), draws one rng_normals<D> per step, and for i = 0..S-1
+//   s, J = score(x, tau_i)                  J[k][n] = ds_k/dx_n
+//   x0h  = (x + v_i s) / alpha_i            (Tweedie)
+//   r    = y' - A x0h                       y' = y - b: p.yres
+//   u    = B_i^T r                          B_i: row min(i, n_B - 1) of the host's table
+//   G    = -(u + v_i J^T u) / alpha_i
+//   lam  = zeta delta beta_i (step_rule 0)  or  zeta / sqrt(max(|r|^2, 1e-30)) (step_rule 1)
+//   x   <- em_update(x, fl(g_i s), xi) - fl(lam G)
+// Sums run over the measurement index first to last, each product rounded (nothing is contracted). A, B_i and y' are
+// wave-uniform: plain loads the compiler may issue as scalar ones. Every lane of a row holds its state and does the
+// same arithmetic; the only stores are the final x. `nonfinite` is ORed with "a kept row's final state is not finite".
+template <int D, int NW, typename Score>
+__device__ __forceinline__ void dps_linear_rows(const DpsLinearChains& p, Rows<NW>& rows, int yi, bool& nonfinite,
+                                                Score&& score) {
+  const int S = p.num_steps, M = p.ydim;
+  const float* yr = p.yres + (size_t)yi * M;
+  for (long long rd = 0; rd < rows.rounds; ++rd) {
+    rows.seek(rd);
+    Rng rng = rng_init(p.seed, (uint64_t)(p.chain_offset + rows.rr), (uint64_t)yi);
+    float x[D];
+    {
+      float n0[D];
+      rng_normals<D>(rng, n0);
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const float xv = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+        x[k] = rows.valid ? xv : 0.0f;  // idle columns compute on zeros and are not stored
+      }
+    }
+    for (int i = 0; i < S; ++i) {
+      const StepCoef c = step_coef(i, S, p.T, p.bmin, p.bdiff);
+      float s[D], J[D][D];
+      score(x, c, s, J);
+      const float mw = vp_mean_weight(c.tau, p.bmin, p.bdiff);
+      const float var = vp_var(c.tau, p.bmin, p.bdiff);
+      float x0h[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) x0h[k] = (x[k] + var * s[k]) / mw;
+      const float* Bi = p.B + (size_t)(p.n_B == 1 ? 0 : i) * M * D;
+      float u[D], rr = 0.0f;
+#pragma unroll
+      for (int k = 0; k < D; ++k) u[k] = 0.0f;
+#pragma unroll 4
+      for (int q = 0; q < M; ++q) {
+        float ax = p.A[q * D] * x0h[0];
+#pragma unroll
+        for (int k = 1; k < D; ++k) ax = ax + p.A[q * D + k] * x0h[k];
+        const float r = yr[q] - ax;
+        rr = rr + r * r;
+#pragma unroll
+        for (int k = 0; k < D; ++k) u[k] = u[k] + Bi[q * D + k] * r;
+      }
+      const float lam = p.step_rule == 0 ? p.zeta * p.delta * c.beta : p.zeta / sqrtf(fmaxf(rr, 1e-30f));
+      float xi[D];
+      rng_normals<D>(rng, xi);
+      float xn[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        float jt = u[k];
+#pragma unroll
+        for (int r = 0; r < D; ++r) jt = jt + var * J[r][k] * u[r];
+        const float G = -(jt / mw);
+        const float xe = em_update(x[k], __fmul_rn(c.g, s[k]), xi[k], c, p.delta, p.sqrt_delta);
+        xn[k] = xe - lam * G;
+      }
+#pragma unroll
+      for (int k = 0; k < D; ++k) x[k] = xn[k];
+    }
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < D; ++k) finite &= __builtin_isfinite(x[k]);
+    nonfinite |= rows.valid && !finite;
+    if (rows.stores()) {
+      const size_t o = (size_t)yi * p.n + rows.row;
+#pragma unroll
+      for (int k = 0; k < D; ++k) p.x_out[o * D + k] = x[k];
+    }
+  }
+}
+
 }  // namespace flow
 
 // ----------------------------------------------------------------- launch helpers (per TU)

@@ -462,6 +462,36 @@ hipError_t launch_x3_flow(const X3FlowParams& p, int mode, int width, int n_hidd
                           hipStream_t st, bool* supported);
 hipError_t launch_x3_flow_sample(const X3FlowSampleParams& p, int mode, int width, int n_hidden, int xdim, int ydim,
                                  int n_y, hipStream_t st, bool* supported);
+// Guided posterior sampling for a linear-Gaussian problem y = A x + b + eta from a prior score network alone
+// (dmip_flow_rows.h dps_linear_rows; dmip_dps_linear.hip in exact f32, dmip_x3_dps_linear.hip in fp32x3). The kernels
+// know a table and two step rules, not the guidance that built the table (include/dmip.h dmip_dps_linear_sample).
+constexpr int kDpsLinearMaxY = 32;
+struct DpsLinearChains {
+  const float* A;             // [ydim][D]
+  const float* B;             // [n_B][ydim][D]: the step's guidance matrix (n_B = 1: one matrix for every step)
+  const float* yres;          // [n_y][ydim]: y - b
+  float* x_out;               // [n_y][n][D]
+  long long n, chain_offset;  // chains per y; the RNG's chain index of row 0
+  int num_steps, ydim, n_B;
+  int step_rule;              // 0: lambda_i = zeta delta beta_i, 1: lambda = zeta / |r|
+  float T, bmin, bdiff, delta, sqrt_delta, mean, stdv, zeta;
+  unsigned long long seed;
+};
+struct F32DpsLinearParams {
+  F32Net net;                 // the prior (x, t) network
+  int n_hidden;
+  DpsLinearChains chains;
+};
+struct X3DpsLinearParams {
+  X3Net net;
+  int n_hidden;
+  DpsLinearChains chains;
+  unsigned int* err;          // device status word (kErrRange)
+};
+// every DMIP_FLOW_SHAPES shape, 1 to 3 hidden layers, ydim 1 to kDpsLinearMaxY, on both engines
+bool dps_linear_supported(int width, int n_hidden, int xdim, int ydim);
+hipError_t launch_f32_dps_linear(const F32DpsLinearParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+hipError_t launch_x3_dps_linear(const X3DpsLinearParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 // geometry of the x3 images (dmip_x3.h Shape) for the host packer
 int x3_chunk_bytes(int width);
 int x3_tiles_per_chunk(int width);

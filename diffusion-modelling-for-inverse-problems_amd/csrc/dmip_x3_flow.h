@@ -181,6 +181,36 @@ __device__ __forceinline__ void flow_score(typename C::E& eng, const int& g, con
   flow::gather_score<MODE, D>(out, j, cf, a, dv);
 }
 
+// flow_score's network half for a one-network configuration, the output tile itself: rows 0..15 of net 0 over the 16
+// columns (s_k of the primal columns, ds_k/dx_{m-1} of the tangent columns), for a caller that keeps every tangent
+// entry (flow::gather_jac; dmip_x3_dps_linear.hip). `kept`, `oor` as flow_score's
+template <typename C, int D, typename Coef>
+__device__ __forceinline__ f32x4 flow_out(typename C::E& eng, const int& g, const int& m, const float (&xin)[D],
+                                          const Coef& cf, const bool& kept, bool& oor) {
+  static_assert(C::K1Q == 1 && C::NV == D + 1 && C::NNET == 1, "one network, layer 1 over (x, tau): one k-step");
+  float v[D + 1];
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = xin[k];
+  v[D] = cf.tau;
+  oor |= kept && out_of_range(v);
+  u32x4 b1[1];
+  l1_operand<D + 1, 1>(v, g, b1);
+  {
+    // the tangent column of input n = m - 1: fp16 1.0 at k-slots 3n and 3n + 2 (this lane supplies slots 8 g + e)
+    const int n = m - 1;
+    f16x8 u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int s = 8 * g + e;
+      u[e] = (n < D && (s == 3 * n || s == 3 * n + 2)) ? (_Float16)1.0f : (_Float16)0.0f;
+    }
+    const u32x4 ub = __builtin_bit_cast(u32x4, u);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) b1[0][e] = m == 0 ? b1[0][e] : ub[e];
+  }
+  return flow_eval<C>(eng, m, 0, b1);
+}
+
 // the sampler kernel's set-up: layer-1 images and biases into LDS (net 0's layer-1 bias is the per-y one), ring started
 template <typename C, int W>
 __device__ __forceinline__ void flow_setup(typename C::E& eng, char* lds, const X3Net (&net)[2], const float* bias_y,

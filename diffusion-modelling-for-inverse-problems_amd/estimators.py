@@ -6,7 +6,8 @@ reverse-SDE kernel for all num_steps, the chain state never leaving the register
   * CDE: dmip_em_sample;
   * PosteriorDiffusionEstimator: dmip_em_sample_posterior (prior + likelihood networks in one kernel);
   * CDiffE (repaired sampler): dmip_em_sample_cdiffe;
-  * DPS (BASELINE config 4, prior score net + forward-model guidance): dmip_dps_sample.
+  * DPS (BASELINE config 4, prior score net + forward-model guidance): dmip_dps_sample;
+  * LinearDPS (a prior score net guided towards a linear-Gaussian measurement): dmip_dps_linear_sample.
 CDE and PosteriorDiffusionEstimator sample the whole lambda family of the reference's PluginReverseSDE
 (sdes.py:77-87) with `lmbd=`: 0 the reverse SDE (the default), 1 the deterministic probability-flow ODE
 (dmip_em_sample_lmbd), and `model.log_prob(x, y)` is the model's own log-density log p(x | y) along that ODE
@@ -680,7 +681,35 @@ class _PriorDrift(nn.Module):
         return self.forward_sde.g(t, x) * self.prior_net(x, t)
 
 
-class DPS(BaseClassDiffusionModel):
+class _PriorDiffusionModel(BaseClassDiffusionModel):
+    """What the guided samplers share (DPS, LinearDPS): a prior score network MLP2(x, t) under the unconditional drift
+    g prior(x, t), trained by the prior DSM."""
+
+    def _init_prior(self, hidden_layers):
+        forward_process = sdes.VariancePreservingSDE()
+        prior_net = MLP2(self.xdim + 1, self.xdim, hidden_layers, nn.Tanh()).to(device)
+        self.sde = sdes.PluginReverseSDE(forward_process, _PriorDrift(prior_net, forward_process), T=1, debias=True)
+
+    @property
+    def prior_net(self):
+        return self.sde.a.prior_net
+
+    def _load_prior(self, pn):
+        """The weights of another model's prior network, on its device."""
+        self.sde.a.prior_net.load_state_dict(pn.state_dict())
+        self.sde.a.prior_net.to(next(pn.parameters()).device)
+        return self
+
+    def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
+        """Prior DSM epoch (the prior half of PosteriorLoss, losses.py:373-377): score = prior(x_t, t)."""
+        def batch_loss(x, y):
+            t = self.sample_t(x)
+            x_t, target, std, g = self.sde.base_sde.sample(t, x, return_noise=True)
+            return loss_fn(self.sde.a.prior_net(x_t, t), std, target).mean()
+        return self._train_loop(optimizer, epoch_data_loader, batch_loss)
+
+
+class DPS(_PriorDiffusionModel):
     """Diffusion posterior sampling (Chung et al. 2023; BASELINE config 4) for the scatterometry problem:
     a prior score network MLP2(x, t) (the PosteriorDiffusionEstimator's prior, trained with DSM as
     PosteriorLoss trains it, losses.py:373-377) guided at every EM step by the gradient of the
@@ -698,9 +727,7 @@ class DPS(BaseClassDiffusionModel):
 
     def __init__(self, xdim, ydim, hidden_layers, forward_model=None, params=None, zeta=0.005, guidance='norm'):
         super().__init__(xdim, ydim)
-        forward_process = sdes.VariancePreservingSDE()
-        prior_net = MLP2(xdim + 1, xdim, hidden_layers, nn.Tanh()).to(device)
-        self.sde = sdes.PluginReverseSDE(forward_process, _PriorDrift(prior_net, forward_process), T=1, debias=True)
+        self._init_prior(hidden_layers)
         self.forward_model = forward_model
         self.params = dict(params or {'a': 0.2, 'b': 0.01, 'lambd_bd': 1000})
         self.zeta = float(zeta)
@@ -708,18 +735,11 @@ class DPS(BaseClassDiffusionModel):
             raise ValueError("guidance must be 'nll' or 'norm'")
         self.guidance = guidance
 
-    @property
-    def prior_net(self):
-        return self.sde.a.prior_net
-
     @classmethod
     def from_posterior(cls, model, forward_model, params=None, zeta=0.005, guidance='norm'):
         """A DPS sampler on the prior network of a trained PosteriorDiffusionEstimator."""
         pn = model.sde.a.prior_net
-        m = cls(model.xdim, model.ydim, pn.hidden_layers, forward_model, params, zeta, guidance)
-        m.sde.a.prior_net.load_state_dict(pn.state_dict())
-        m.sde.a.prior_net.to(next(pn.parameters()).device)
-        return m
+        return cls(model.xdim, model.ydim, pn.hidden_layers, forward_model, params, zeta, guidance)._load_prior(pn)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, noise=None,
                       precision=None, lmbd=0.0, solver="euler", x0=None):
@@ -748,10 +768,141 @@ class DPS(BaseClassDiffusionModel):
                         precision="fp32" if prec == "fp32" else "fp32x3")
         return out
 
-    def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
-        """Prior DSM epoch (the prior half of PosteriorLoss, losses.py:373-377): score = prior(x_t, t)."""
-        def batch_loss(x, y):
-            t = self.sample_t(x)
-            x_t, target, std, g = self.sde.base_sde.sample(t, x, return_noise=True)
-            return loss_fn(self.sde.a.prior_net(x_t, t), std, target).mean()
-        return self._train_loop(optimizer, epoch_data_loader, batch_loss)
+
+_LINEAR_GUIDANCES = ('pigdm', 'nll', 'norm')
+
+
+def _spd_matrix(Sigma, M):
+    """Sigma (a scalar, a length-M diagonal or an M x M matrix) as a float64 M x M array; ValueError unless it is
+    symmetric positive definite."""
+    S = np.asarray(1.0 if Sigma is None else (Sigma.detach().cpu().numpy() if isinstance(Sigma, torch.Tensor)
+                                              else Sigma), np.float64)
+    if S.ndim == 0:
+        S = float(S) * np.eye(M)
+    elif S.shape == (M,):
+        S = np.diag(S)
+    elif S.shape != (M, M):
+        raise ValueError(f"Sigma must be a scalar, a length-{M} diagonal or a {M} x {M} matrix, got shape {S.shape}")
+    if not np.all(np.isfinite(S)) or not np.allclose(S, S.T, rtol=1e-12, atol=0.0):
+        raise ValueError("Sigma must be finite and symmetric")
+    try:
+        np.linalg.cholesky(S)
+    except np.linalg.LinAlgError:
+        raise ValueError("Sigma must be symmetric positive definite") from None
+    return S
+
+
+def linear_guidance_table(A, Sigma, guidance, num_steps, beta_min, beta_max, T):
+    """The guidance table of dmip_dps_linear_sample in float64: (B [n_B][M][D], step rule).
+      'pigdm'  B_i = (Sigma + v_i A A^T)^-1 A for every step of the reverse grid, lambda_i = zeta delta beta_i
+      'nll'    B = Sigma^-1 A, one matrix, the same rule
+      'norm'   B = 2 A, one matrix, lambda = zeta / |r|
+    v_i = var(tau_i) = 1 - exp(-tau_i^2 (beta_max - beta_min) / 2 - tau_i beta_min) at the samplers' f32 times
+    tau_i = T - T linspace(0, 1, S + 1)[i]."""
+    A = np.asarray(A, np.float64)
+    if guidance == 'norm':
+        return 2.0 * A[None], _lib.DMIP_DPS_STEP_NORM
+    if guidance == 'nll':
+        return np.linalg.solve(Sigma, A)[None], _lib.DMIP_DPS_STEP_BETA
+    if guidance != 'pigdm':
+        raise ValueError(f"guidance must be one of {_LINEAR_GUIDANCES}")
+    S = int(num_steps)
+    Tf = torch.tensor(float(T), dtype=torch.float32)
+    tau = (Tf - torch.linspace(0, 1, S + 1, dtype=torch.float32) * Tf)[:S].double().numpy()  # the kernels' step_coef
+    v = -np.expm1(-0.5 * tau * tau * (float(beta_max) - float(beta_min)) - tau * float(beta_min))
+    AAt = A @ A.T
+    return np.stack([np.linalg.solve(Sigma + vi * AAt, A) for vi in v]), _lib.DMIP_DPS_STEP_BETA
+
+
+class LinearDPS(_PriorDiffusionModel):
+    """Guided posterior sampling for a linear-Gaussian problem y = A x + b + eta, eta ~ N(0, Sigma), from a prior score
+    network MLP2(x, t) alone: one trained prior serves every A, b, Sigma and y. Per step, at the Tweedie estimate
+    x0_hat = (x + var s) / mean_weight, the residual r = y - b - A x0_hat enters the EM step through
+    G = -(I + var J^T) B_i^T r / mean_weight (J = ds/dx, all of it, from the network's forward tangents):
+      guidance='pigdm' (default)  B_i = (Sigma + var(tau_i) A A^T)^-1 A: the likelihood of y given x_tau with the
+                                  covariance of x0 given x_tau kept; exact for a Gaussian prior
+      guidance='nll'              B = Sigma^-1 A: the DPS likelihood, which drops that term
+      guidance='norm'             B = 2 A with the step zeta / ||r|| (Chung et al. Alg. 1)
+    Fused kernel: dmip_dps_linear_sample (include/dmip.h), one launch for all steps, for every network shape of the
+    flow kernels (widths 64 to 512, 1 to 3 hidden layers, xdim 2 or 3) and ydim up to 32; there is no per-step path.
+
+    A (ydim, xdim); b (ydim,) or None (zero); Sigma a scalar, a (ydim,) diagonal or a (ydim, ydim) matrix (None: the
+    identity), symmetric positive definite."""
+
+    def __init__(self, xdim, ydim, hidden_layers, A, b=None, Sigma=None, zeta=1.0, guidance='pigdm'):
+        super().__init__(xdim, ydim)
+        if not 1 <= int(ydim) <= 32:
+            raise ValueError(f"LinearDPS: ydim must be in [1, 32], got {ydim}")
+        if guidance not in _LINEAR_GUIDANCES:
+            raise ValueError(f"guidance must be one of {_LINEAR_GUIDANCES}")
+        as64 = lambda v: np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float64)
+        self.A = as64(A)
+        if self.A.shape != (ydim, xdim):
+            raise ValueError(f"A must have shape (ydim, xdim) = ({ydim}, {xdim}), got {self.A.shape}")
+        self.b = np.zeros(ydim) if b is None else as64(b).reshape(-1)
+        if self.b.shape != (ydim,):
+            raise ValueError(f"b must have {ydim} entries, got {self.b.size}")
+        if not (np.all(np.isfinite(self.A)) and np.all(np.isfinite(self.b))):
+            raise ValueError("A and b must be finite")
+        self.Sigma = _spd_matrix(Sigma, ydim)
+        zeta = float(zeta)
+        if not (zeta >= 0.0 and np.isfinite(zeta)):
+            raise ValueError(f"zeta must be finite and >= 0, got {zeta}")
+        self.zeta = zeta
+        self.guidance = guidance
+        self._init_prior(hidden_layers)
+        self._table = None       # (key, A, B, b, step rule): device tensors of the last (num_steps, SDE, guidance, device)
+        self.table_uploads = 0   # instrumentation: how often the table went to a device
+
+    @classmethod
+    def from_posterior(cls, model, A, b=None, Sigma=None, zeta=1.0, guidance='pigdm'):
+        """A LinearDPS sampler on the prior network of a trained PosteriorDiffusionEstimator (or DPS / LinearDPS)."""
+        pn = model.sde.a.prior_net
+        return cls(model.xdim, int(np.shape(A)[0]), pn.hidden_layers, A, b, Sigma, zeta, guidance)._load_prior(pn)
+
+    @classmethod
+    def for_problem(cls, problem, hidden_layers, zeta=1.0, guidance='pigdm'):
+        """The sampler of a LinearForwardProblem: its A, b and Sigma."""
+        return cls(problem.xdim, problem.ydim, hidden_layers, problem.A, problem.b, problem.Sigma, zeta, guidance)
+
+    def guidance_table(self, num_steps, dev):
+        """(A, B, b, step rule) on `dev`: A (ydim, xdim) and B (n_B, ydim, xdim) as f32 (built in float64, rounded
+        once), b as float64 (y - b is formed in float64 and rounded once). Cached on the model for the last
+        (num_steps, SDE, guidance, device): repeated calls upload nothing."""
+        base = self.sde.base_sde
+        key = (int(num_steps), float(base.beta_min), float(base.beta_max), float(self.sde.T), self.guidance, str(dev))
+        if self._table is None or self._table[0] != key:
+            B, rule = linear_guidance_table(self.A, self.Sigma, self.guidance, num_steps, base.beta_min, base.beta_max,
+                                            self.sde.T)
+            up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(v)).to(dt).to(dev).contiguous()
+            self._table = (key, up(self.A, torch.float32), up(B, torch.float32), up(self.b, torch.float64), rule)
+            self.table_uploads += 1
+        return self._table[1:]
+
+    def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, noise=None,
+                      precision=None, lmbd=0.0, solver="euler", x0=None):
+        """dmip_dps_linear_sample at `precision` (default self.precision): "fp32x3" (also what "fp16" runs: there is
+        no 16-bit kernel) or "fp32" (exact f32). At the default precision a chain outside fp16's range resamples in
+        exact f32 (parallel.sample_checked). A shape without a kernel raises ValueError."""
+        _check_solver(solver, lmbd, self, x0)
+        if noise is not None:
+            raise ValueError("noise injection is only implemented for the fused CDE sampler")
+        if int(num_samples) < 1 or int(num_steps) < 1:
+            raise ValueError("LinearDPS: num_samples and num_steps must be >= 1")
+        prec = canonical_precision(precision or self.precision)
+        _lib.precision_code(prec)
+        prec = "fp32" if prec == "fp32" else "fp32x3"
+        pn = self.prior_net
+        dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [pn])
+        layers = pn.hidden_layers
+        if len(set(layers)) != 1 or pn.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST or \
+                not _lib.dps_linear_supported(layers[0], len(layers), self.xdim, self.ydim, prec):
+            raise ValueError(f"LinearDPS: no compiled kernel for hidden layers {layers}, xdim {self.xdim}, ydim "
+                             f"{self.ydim} (equal widths 64 / 128 / 256 / 512, 1 to 3 layers, xdim 2 or 3, nn.Tanh)")
+        prior = pn.dmip_handle(dev, self.xdim)
+        A, B, b, rule = self.guidance_table(num_steps, dev)
+        yres = (ys.double() - b).float().contiguous()
+        seed = _draw_seed() if seed is None else seed
+        _lib.dps_linear_sample(prior, sde, A, B, yres, num_samples, chain_offset, num_steps, mean, std, seed, rule,
+                               self.zeta, out, precision=prec)
+        return out

@@ -2,8 +2,10 @@
 
 Extension (not in the reference): config['model'] == 'DPS' builds the guided sampler of BASELINE config 4
 (estimators.DPS) on `forward_model`, with optional config keys 'zeta' (default 0.005) and 'guidance'
-('norm' | 'nll', default 'norm'); its training loss is the prior DSM (DSMLoss)."""
-from .estimators import CDE, DPS, CDiffE, PosteriorDiffusionEstimator
+('norm' | 'nll', default 'norm'); its training loss is the prior DSM (DSMLoss). config['model'] == 'LinearDPS' builds
+estimators.LinearDPS for the linear problem: `forward_model` is the problem object (LinearForwardProblem: its A, b and
+Sigma), the keys are 'zeta' (default 1.0) and 'guidance' ('pigdm' | 'nll' | 'norm', default 'pigdm'), the loss DSMLoss."""
+from .estimators import CDE, DPS, CDiffE, LinearDPS, PosteriorDiffusionEstimator
 from .losses import DSM_PDELoss, DSMLoss, PINNLoss, PINNLoss2
 
 _MODELS = {'CDE': CDE, 'CDiffE': CDiffE, 'Posterior': PosteriorDiffusionEstimator}
@@ -13,6 +15,10 @@ def get_model_from_args(config, forward_model_params, score_posterior, forward_m
     if config['model'] == 'DPS':
         model = DPS(forward_model_params['xdim'], forward_model_params['ydim'], config['hidden_layers'], forward_model,
                     forward_model_params, zeta=config.get('zeta', 0.005), guidance=config.get('guidance', 'norm'))
+        return model, DSMLoss()
+    if config['model'] == 'LinearDPS':
+        model = LinearDPS.for_problem(forward_model, config['hidden_layers'], zeta=config.get('zeta', 1.0),
+                                      guidance=config.get('guidance', 'pigdm'))
         return model, DSMLoss()
     cls = _MODELS.get(config['model'])
     if cls is None:

@@ -489,6 +489,37 @@ int dmip_dps_sample_ex(const dmip_mlp* prior, const dmip_surrogate* fwd, const d
                        int num_steps, float mean, float stdv, uint64_t seed, int mode, float zeta, int precision,
                        float* x_out_dev, void* stream);
 
+/* Guided posterior sampling for a linear-Gaussian problem y = A x + b + eta, eta ~ N(0, Sigma), from a prior score
+ * network alone (ABI 9, additive): the DPS step above with the forward model a matrix, for every network shape of the
+ * flow kernels. D = xdim (2 or 3, the prior's), M = ydim in [1, 32]. Per chain and step i of the samplers' reverse grid
+ * (tau_i, beta_i, g_i; alpha_i = mean_weight(tau_i), v_i = var(tau_i), delta = T / num_steps):
+ *   s, J = prior(x, tau_i) and ds/dx      (every entry of J from three forward tangents, one network pass)
+ *   x0_hat = (x + v_i s) / alpha_i;  r = y' - A x0_hat;  u = B_i^T r;  G = -(u + v_i J^T u) / alpha_i
+ *   x <- x + delta (g_i^2 s + beta_i x / 2) + sqrt(delta) g_i xi  -  lambda_i G
+ *   step_rule DMIP_DPS_STEP_BETA: lambda_i = zeta delta beta_i;  DMIP_DPS_STEP_NORM: lambda_i = zeta / ||r||
+ * The kernel knows the table B and the step rule, not the guidance that built them; the Python estimator LinearDPS
+ * builds B in float64: (Sigma + v_i A A^T)^-1 A per step (covariance-corrected, exact for a Gaussian prior), Sigma^-1 A
+ * (the DPS likelihood), or 2 A with DMIP_DPS_STEP_NORM (Chung et al. Alg. 1).
+ *   prior     MLP2 handle (DMIP_INPUT_X_T, in_dim = xdim + 1, out_dim = xdim), tanh chain
+ *   A_dev     [M][D];  B_dev [n_B][M][D], n_B = 1 (one matrix for every step) or num_steps;  yres_dev [n_y][M] = y - b
+ *   x_out_dev [n_y][n_chains][D]
+ *   precision DMIP_PREC_F32 (exact f32) or DMIP_PREC_F32X3 (DMIP_PREC_FP16 runs it too: there is no 16-bit kernel);
+ *             fp32x3 range as dmip_dps_sample_ex: a weight beyond fp16's range is refused (DMIP_ERR_UNSUPPORTED, "fp16
+ *             range"), a chain's layer-1 input beyond it or a non-finite final state is reported by dmip_device_status
+ * A null pointer, an unknown step rule, num_steps < 1, n_B not 1 or num_steps, ydim outside [1, 32], zeta negative or
+ * not finite, n_y outside [1, 65535], a negative chain count or offset and a prior that is not an x,t network are
+ * DMIP_ERR_INVALID; a SiLU prior, a shape or precision without a kernel and fp32x3 weights beyond fp16's range are
+ * DMIP_ERR_UNSUPPORTED; every argument is validated before any device work. One launch on the static grid of the flow
+ * kernels; RNG and sharding as dmip_em_sample (x0 = mean + stdv n from the first D normals of the chain's stream, then
+ * one draw of D normals per step). dmip_dps_linear_supported: widths 64/128/256/512, 1-3 hidden layers, xdim 2 or 3,
+ * ydim 1 to 32, DMIP_PREC_F32 / F32X3 / FP16. */
+typedef enum { DMIP_DPS_STEP_BETA = 0, DMIP_DPS_STEP_NORM = 1 } dmip_dps_step_rule;
+int dmip_dps_linear_supported(int width, int n_hidden, int xdim, int ydim, int precision);
+int dmip_dps_linear_sample(const dmip_mlp* prior, const dmip_vpsde* sde, const float* A_dev, const float* B_dev, int n_B,
+                           const float* yres_dev, int ydim, int n_y, int64_t n_chains, int64_t chain_offset,
+                           int num_steps, float mean, float stdv, uint64_t seed, int step_rule, float zeta,
+                           int precision, float* x_out_dev, void* stream);
+
 /* ---- PosteriorLoss training step ------------------------------------------ */
 /* Loss value, components and the parameter gradients of PosteriorLoss(forward_model, a, b, lam)(sde, x,
  * y, t) + loss.backward() (losses.py:293-386) as PosteriorDiffusionEstimator.train_epoch drives it
