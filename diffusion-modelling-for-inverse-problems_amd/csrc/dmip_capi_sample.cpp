@@ -41,6 +41,8 @@ struct SampleArgs {
   double lmbd = 0.0;  // sdes.py:77-87: 0 the reverse SDE, 1 the probability-flow ODE (CDE and Posterior)
   int solver = DMIP_SOLVER_EULER;   // DMIP_SOLVER_HEUN: dmip_ode_sample's second-order ODE steps (lmbd = 1)
   const float* x0_dev = nullptr;    // Heun: start states [n_y][n_chains][xdim] in place of randn stdv + mean
+  // dmip_multistep_sample: the step table [num_steps][kMultistepCols]; its launch is SOLVER_TABLE whatever `solver`
+  const float* table_dev = nullptr;
 };
 
 // the VP-SDE schedule of a launch: each value evaluated in double and rounded once to the kernels' f32.
@@ -143,8 +145,9 @@ int em_sample_f32(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sa
   }
   if (int rc = fill_common(p, a, st)) return rc;
   p.act = f32_act(net0);
-  p.solver = a.solver;
+  p.solver = a.table_dev ? dmip::kSolverTable : a.solver;
   p.x0 = a.x0_dev;
+  p.table = a.table_dev;
   bool ok = false;
   hipError_t e = dmip::launch_f32_sampler(p, mode, net0->width, net0->n_hidden, xdim, ydim, a.n_y, st, &ok);
   if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled f32 sampler");
@@ -204,7 +207,8 @@ int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sam
   if (net1) p.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
   p.n_hidden = net0->n_hidden;
   StreamScratch bias_y;
-  const bool heun = a.solver == DMIP_SOLVER_HEUN;  // the one-tile engine only (dmip_x3.h): x3s / x3k keep Euler
+  // Heun and the table-driven multistep sampler: the one-tile engine only (dmip_x3.h); x3s / x3k keep Euler
+  const bool heun = a.solver == DMIP_SOLVER_HEUN || a.table_dev;
   if (!heun && dmip::x3s_sampler_eligible(mode, net0->width, net0->n_hidden, xdim, a.n_chains, a.n_y)) {
     // the width-64 latency engine forms the per-y bias itself (round 6: one launch and one allocation fewer)
     p.l1w = net0->w1;
@@ -216,8 +220,9 @@ int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sam
   }
   p.bias_y = (float*)bias_y.ptr;
   if (int rc = fill_common(p, a, st)) return rc;
-  p.solver = a.solver;
+  p.solver = a.table_dev ? dmip::kSolverTable : a.solver;
   p.x0 = a.x0_dev;
+  p.table = a.table_dev;
   bool ok = false;
   hipError_t e;
 #ifdef DMIP_WITH_X3P
@@ -328,6 +333,11 @@ int em_sample_impl(int mode, const dmip_mlp* net0, const dmip_mlp* prior, const 
             ? dmip::f32_heun_supported(mode, net0->width, net0->n_hidden, xdim, f32_act(net0))
             : dmip_ode_sample_supported(mode, net0->width, net0->n_hidden, xdim, ydim, a.precision, a.solver)))
     return no_kernel("Heun sampler", mode, net0, xdim, -1, a.precision);
+  if (a.table_dev &&
+      !(a.precision == DMIP_PREC_F32
+            ? dmip::f32_multistep_supported(mode, net0->width, net0->n_hidden, xdim, f32_act(net0))
+            : dmip_multistep_supported(mode, net0->width, net0->n_hidden, xdim, ydim, a.precision)))
+    return no_kernel("multistep sampler", mode, net0, xdim, -1, a.precision);
   if (a.n_chains == 0) return DMIP_OK;
   if (a.precision == DMIP_PREC_F32) return em_sample_f32(mode, net0, net1, a);
   if (a.precision == DMIP_PREC_F32X3) return em_sample_x3(mode, net0, net1, a);
@@ -477,6 +487,42 @@ int dmip_ode_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const 
   a.lmbd = 1.0;
   a.solver = DMIP_SOLVER_HEUN;
   a.x0_dev = x0_dev;
+  return em_sample_impl(mode, net, prior, a);
+}
+
+// the table-driven few-step samplers (dmip_device.h MultistepStep): the exact-f32 and the one-tile fp32x3 engines at
+// the shapes of their Heun kernels; the answer is for the tanh chain (as dmip_ode_sample_supported's)
+int dmip_multistep_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR) return 0;
+  if (precision == DMIP_PREC_F32) return dmip::f32_multistep_supported(mode, width, n_hidden, xdim, 0) ? 1 : 0;
+  if (precision == DMIP_PREC_F32X3) return dmip::x3_multistep_supported(mode, width, n_hidden, xdim) ? 1 : 0;
+  return 0;
+}
+
+// DPM-Solver++(2M) / DDIM from a step table; every argument is validated before any device work, in dmip_ode_sample's
+// order. The kernels take every time-dependent quantity from the table, so there is no dmip_vpsde here
+int dmip_multistep_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev, int n_y, int ydim,
+                          int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, const float* table_dev,
+                          int table_cols, float mean, float stdv, uint64_t seed, int precision, const float* x0_dev,
+                          int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "multistep_sample: CDE and Posterior samplers only");
+  if (table_cols != DMIP_MULTISTEP_COLS)
+    return fail(DMIP_ERR_INVALID, "multistep_sample: table_cols must be DMIP_MULTISTEP_COLS");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (int rc = check_snapshots(snapshot_every, num_steps, snap_out_dev)) return rc;
+  if (!net || !table_dev || !y_dev || !x_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
+    return fail(DMIP_ERR_INVALID, "null argument");
+  if (precision == DMIP_PREC_FP16)
+    return fail(DMIP_ERR_UNSUPPORTED, "multistep_sample: no 16-bit kernel (DMIP_PREC_F32X3 or DMIP_PREC_F32)");
+  static const dmip_vpsde no_sde{0.0, 0.0, 1.0};  // (the launch's schedule fields are unused by SOLVER_TABLE)
+  SampleArgs a(&no_sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv, seed, precision,
+               x_out_dev, stream);
+  a.snap_every = snapshot_every;
+  a.snap_out_dev = snapshot_every > 0 ? snap_out_dev : nullptr;
+  a.lmbd = 1.0;
+  a.x0_dev = x0_dev;
+  a.table_dev = table_dev;
   return em_sample_impl(mode, net, prior, a);
 }
 

@@ -164,7 +164,8 @@ __device__ __forceinline__ float em_update(float x, float a, float xi, const Ste
 // from a buffer), so one seed starts the Euler and the Heun chains from the same x0. For the Posterior estimator
 // a = fl(g_i (lik + prior)) at each stage's own g, as the Euler loop forms it. Both engines (dmip_x3.h,
 // dmip_f32.h) take their arithmetic from here.
-enum { SOLVER_EULER = 0, SOLVER_HEUN = 1 };
+// SOLVER_TABLE (internal: not a value of the C-ABI's dmip_solver) is the table-driven multistep sampler below.
+enum { SOLVER_EULER = 0, SOLVER_HEUN = 1, SOLVER_TABLE = 2 };
 
 struct HeunStep {
   // m(x, i): the drift of em_update at the coefficients c
@@ -178,6 +179,55 @@ struct HeunStep {
     return __fadd_rn(x, __fmul_rn(__fmul_rn(0.5f, delta), __fadd_rn(k1, k2)));
   }
 };
+
+// The few-step samplers of the probability-flow ODE in data-prediction form: DPM-Solver++(2M) (Lu et al. 2022) and
+// its first-order case DDIM, on any decreasing grid tau_0 = T > ... > tau_{S-1} > tau_S = 0 (uniform in the log-SNR
+// lambda = log(alpha / sigma) by default). One network evaluation per step and no draw. With alpha_i, sigma_i the VP
+// mean weight and std at tau_i, g_i = sqrt(beta(tau_i)), h_i = lambda_{i+1} - lambda_i and a = g score:
+//     d_i     = (x_i + (sigma_i^2 / g_i) a_i) / alpha_i                              the denoised estimate
+//     x_{i+1} = (sigma_{i+1} / sigma_i) x_i - alpha_{i+1} expm1(-h_i) D_i
+//     D_i     = d_i (DDIM, and step 0)  |  (1 + 1/(2r)) d_i - (1/(2r)) d_{i-1}, r = h_{i-1} / h_i   (2M)
+//     x_S     = d_{S-1}                                                              the last step (sigma_S = 0)
+// Everything that depends on time comes from a host table (float64, rounded once), one row of kMultistepCols floats
+// per step: tau | p q (d = p x + q a) | cx c0 c1 (x' = cx x + c0 d + c1 d_prev) | g (the Posterior's a = g (lik +
+// prior)) | 0. The kernels compute nothing from tau but the network's input, so a non-default VP-SDE enters through
+// the table alone, and DDIM is the same kernel at c1 = 0. The f32 rounding order of the two updates is fixed here
+// (no FMA), for both engines and for the numpy restatement (tests/multistep_ref.py):
+//     d  = fl(fl(p x) + fl(q a))
+//     x' = fl(fl(fl(cx x) + fl(c0 d)) + fl(c1 d_prev))
+// d_prev starts at 0 (c1 = 0 in row 0), stays in registers, and crosses a hand-over in the slot's RNG words, which
+// are dead after x0 for this solver.
+constexpr int kMultistepCols = 8;
+
+struct MultistepStep {
+  float tau, p, q, cx, c0, c1, g;
+
+  // row i of the table, by scalar loads: i is wave-uniform and the table constant for the launch (constant address
+  // space: the compiler may not take a uniform load of plain global memory for scalar beside the kernel's stores)
+  static __device__ __forceinline__ MultistepStep load(const float* table, int i) {
+    typedef __attribute__((address_space(4))) const float* const_fptr;
+    const const_fptr r = (const_fptr)(table + (size_t)i * kMultistepCols);
+    return MultistepStep{r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
+  }
+  __device__ __forceinline__ float denoise(float x, float a) const {
+    return __fadd_rn(__fmul_rn(p, x), __fmul_rn(q, a));
+  }
+  __device__ __forceinline__ float advance(float x, float d, float d_prev) const {
+    return __fadd_rn(__fadd_rn(__fmul_rn(cx, x), __fmul_rn(c0, d)), __fmul_rn(c1, d_prev));
+  }
+};
+
+// d_prev of a chain, zero before step 0; N = 0 (every other solver) holds nothing
+template <int N>
+struct MultistepHist {
+  float d[N];
+  __device__ __forceinline__ MultistepHist() {
+#pragma unroll
+    for (int k = 0; k < N; ++k) d[k] = 0.0f;
+  }
+};
+template <>
+struct MultistepHist<0> {};
 
 // Trajectory snapshots: x of a chain after every `every`-th step (0-based step i, i + 1 a multiple
 // of every) into snap [S / every][n_y][n_chains][D] -- the only HBM writes of a chain before its final

@@ -41,6 +41,11 @@ hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, in
     if (mode == SAMPLER_CDE) return launch_f32_sampler_cde_heun(p, width, xdim, n_y, st, supported);
     return launch_f32_sampler_post_heun(p, width, xdim, n_y, st, supported);
   }
+  if (p.solver == SOLVER_TABLE) {
+    if (!f32_multistep_supported(mode, width, n_hidden, xdim, p.act)) return hipSuccess;
+    if (mode == SAMPLER_CDE) return launch_f32_sampler_cde_ms(p, width, xdim, n_y, st, supported);
+    return launch_f32_sampler_post_ms(p, width, xdim, n_y, st, supported);
+  }
   if (mode == SAMPLER_CDE) return launch_f32_sampler_cde(p, width, xdim, n_y, st, supported);
   if (mode == SAMPLER_POSTERIOR) return launch_f32_sampler_post(p, width, xdim, n_y, st, supported);
   return launch_f32_sampler_cdiffe(p, width, xdim, ydim, n_y, st, supported);
@@ -64,6 +69,12 @@ bool f32_heun_supported(int mode, int width, int n_hidden, int xdim, int act) {
   if (mode != SAMPLER_CDE && mode != SAMPLER_POSTERIOR) return false;
   if (width == 512 && !(mode == SAMPLER_CDE && act != 0)) return false;
   return f32_sampler_supported(mode, width, n_hidden, xdim, 0);
+}
+
+// The table-driven multistep sampler (dmip_device.h MultistepStep): the shapes of the Heun units (width 512 with the
+// tanh chain would need scratch there too)
+bool f32_multistep_supported(int mode, int width, int n_hidden, int xdim, int act) {
+  return f32_heun_supported(mode, width, n_hidden, xdim, act);
 }
 
 // layer-1 k-steps: 2 (in_dim <= 7: every x,t and the linear problem's x,y,t network) or 8 (in_dim

@@ -77,6 +77,10 @@ constexpr unsigned kErrHandover = 1u;
 // resample with the exact-f32 engine)
 constexpr unsigned kErrRange = 2u;
 
+// F32SamplerParams / X3SamplerParams::solver of the table-driven multistep sampler, for the host layer (the kernels'
+// SOLVER_TABLE of dmip_device.h; dmip_solver's values name the other two)
+constexpr int kSolverTable = 2;
+
 // hand-over state of a split tile, per grid wave: x[D] + the xoshiro128** state, one word per lane
 constexpr int sampler_xfer_words(int D) { return (D + 4) * 64; }
 // zeroed hand-over buffers for `slots` grid waves (freed by the caller with hipFreeAsync(*buf))
@@ -292,8 +296,9 @@ struct F32SamplerParams {
   int debug_flags;
   int act;                    // 0 tanh, 1 SiLU (dmip_act: the activation chain; SiLU for SAMPLER_CDE only)
   // the Heun ODE sampler (dmip_device.h HeunStep; host side: selects the launch_*_heun instantiations)
-  int solver;                 // SOLVER_EULER / SOLVER_HEUN
-  const float* x0;            // Heun: start states [n_y][n_chains][D] or null (randn stdv + mean from the RNG)
+  int solver;                 // SOLVER_EULER / SOLVER_HEUN / SOLVER_TABLE
+  const float* x0;            // Heun, multistep: start states [n_y][n_chains][D] or null (randn stdv + mean from the RNG)
+  const float* table;         // SOLVER_TABLE: [num_steps][kMultistepCols] step rows (dmip_device.h MultistepStep)
 };
 
 struct F32ForwardParams {
@@ -365,6 +370,7 @@ hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, in
                               int n_y, hipStream_t st, bool* supported);
 bool f32_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 bool f32_heun_supported(int mode, int width, int n_hidden, int xdim, int act);
+bool f32_multistep_supported(int mode, int width, int n_hidden, int xdim, int act);
 hipError_t launch_f32_forward(const F32ForwardParams& p, int width, int ot, hipStream_t st, bool* supported);
 hipError_t launch_f32_l1_prep(const F32L1PrepParams& p, int n_y, hipStream_t st);
 
@@ -413,8 +419,9 @@ struct X3SamplerParams {
   const float* l1b;
   int l1_in, ydim;
   // the Heun ODE sampler (dmip_device.h HeunStep; the one-tile engine only: dmip_x3.h)
-  int solver;                 // SOLVER_EULER / SOLVER_HEUN
-  const float* x0;            // Heun: start states [n_y][n_chains][D] or null (randn stdv + mean from the RNG)
+  int solver;                 // SOLVER_EULER / SOLVER_HEUN / SOLVER_TABLE
+  const float* x0;            // Heun, multistep: start states [n_y][n_chains][D] or null (randn stdv + mean from the RNG)
+  const float* table;         // SOLVER_TABLE: [num_steps][kMultistepCols] step rows (dmip_device.h MultistepStep)
 };
 // the latency engine takes this launch (CDE, width 64, xdim 2 or 3, 1-3 hidden layers, <= 1,024 tiles over all ys;
 // DMIP_X3_SPLIT=0 opts out): launch_x3_sampler_cde's own test, exposed so the caller can skip the bias prep
@@ -432,6 +439,7 @@ hipError_t launch_x3_sampler(const X3SamplerParams& p, int mode, int width, int 
                              hipStream_t st, bool* supported);
 bool x3_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 bool x3_heun_supported(int mode, int width, int n_hidden, int xdim);
+bool x3_multistep_supported(int mode, int width, int n_hidden, int xdim);
 // the k-major multi-tile engine (dmip_x3k.h): CDE, width 256, 3 hidden layers, xdim 2 or 3
 bool x3k_sampler_supported(int mode, int width, int n_hidden, int xdim);
 hipError_t launch_x3k_sampler(const X3SamplerParams& p, int xdim, int n_y, hipStream_t st, bool* ok);

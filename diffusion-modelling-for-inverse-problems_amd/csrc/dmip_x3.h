@@ -565,6 +565,9 @@ __device__ __forceinline__ void report_range(bool oor, unsigned* err, int lane) 
 // SOLVER_HEUN (CDE and Posterior; dmip_x3_{cde,post}_heun.hip): a step is Heun's trapezoid on the probability-flow
 // ODE instead (dmip_device.h HeunStep) -- the network twice, no draw, x0 from p.x0 when given. Schedule, hand-over,
 // ring and snapshots are the Euler kernel's; every Euler instantiation compiles to what it was without the parameter.
+// SOLVER_TABLE (CDE and Posterior; dmip_x3_{cde,post}_ms.hip): a step is DPM-Solver++(2M) / DDIM from the row of a host
+// table (dmip_device.h MultistepStep) -- the network once, no draw, d_prev in D registers and, across a hand-over, in
+// the slot's RNG words.
 template <int MODE, int W, int D, int M, int DIAG = 0>
 struct SamplerCfg {
   static constexpr int NNET = MODE == SAMPLER_POSTERIOR ? 2 : 1;
@@ -642,20 +645,28 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
     };
     Rng rng;
     float x[D];
+    // SOLVER_TABLE: the previous step's denoised estimate (empty otherwise: a dead array here was enough to shift the
+    // other instantiations' register allocation)
+    [[maybe_unused]] MultistepHist<SOLVER == SOLVER_TABLE ? D : 0> hist;
     if (sg.kind == 2) {  // resume the tile the previous wave of the grid handed over
       const size_t slot = (size_t)yi * n_waves + gw - 1;
       const bool lost = handover_wait(p.xflag + slot, p.spin_limit, p.err, kErrHandover, lane);
       const float* src = p.xfer + slot * XW;
 #pragma unroll
       for (int k = 0; k < D; ++k) x[k] = lost ? __builtin_nanf("") : src[k * 64 + lane];
-      rng.s0 = __float_as_uint(src[(D + 0) * 64 + lane]);
-      rng.s1 = __float_as_uint(src[(D + 1) * 64 + lane]);
-      rng.s2 = __float_as_uint(src[(D + 2) * 64 + lane]);
-      rng.s3 = __float_as_uint(src[(D + 3) * 64 + lane]);
+      if constexpr (SOLVER == SOLVER_TABLE) {  // the slot's RNG words carry d_{s0 - 1} (dead after x0 here)
+#pragma unroll
+        for (int k = 0; k < D; ++k) hist.d[k] = src[(D + k) * 64 + lane];
+      } else {
+        rng.s0 = __float_as_uint(src[(D + 0) * 64 + lane]);
+        rng.s1 = __float_as_uint(src[(D + 1) * 64 + lane]);
+        rng.s2 = __float_as_uint(src[(D + 2) * 64 + lane]);
+        rng.s3 = __float_as_uint(src[(D + 3) * 64 + lane]);
+      }
     } else {
       rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
       float n0[D];
-      if constexpr (SOLVER == SOLVER_HEUN) {
+      if constexpr (SOLVER != SOLVER_EULER) {
         // x0 from the caller's buffer [n_y][n_chains][D], else the first draw of the chain's stream (as Euler's)
         if (p.x0) {
           const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
@@ -682,7 +693,11 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
     SnapCursor snap(p.snap_every, sg.s0);
     for (int i0 = sg.s0; i0 < sg.s1; ++i0) {
       const int i = sg.kind == 3 ? 0 : i0;  // idle steps: a dummy tile at step 0, discarded
-      const StepCoef cf = step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
+      // SOLVER_TABLE: the step's row of the host table instead (tau for the network, g for the Posterior's a)
+      MultistepStep ms{};
+      if constexpr (SOLVER == SOLVER_TABLE) ms = MultistepStep::load(p.table, i);
+      const StepCoef cf = SOLVER == SOLVER_TABLE ? StepCoef{ms.tau, 0.0f, ms.g, 0.0f, 0.0f}
+                                                 : step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
       float v[C::NV];
 #pragma unroll
       for (int k = 0; k < D; ++k) v[k] = x[k];
@@ -734,7 +749,17 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
 
       float a[D];
       score(v, a);
-      if constexpr (SOLVER == SOLVER_HEUN) {
+      if constexpr (SOLVER == SOLVER_TABLE) {
+        // DPM-Solver++(2M) / DDIM from the table's row (dmip_device.h MultistepStep): one evaluation, no draw
+        static_assert(MODE != SAMPLER_CDIFFE && !NOISE && D <= 4, "multistep: CDE and Posterior, d_prev in 4 words");
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
+          const float d = ms.denoise(x[k], ak);
+          x[k] = ms.advance(x[k], d, hist.d[k]);
+          hist.d[k] = d;
+        }
+      } else if constexpr (SOLVER == SOLVER_HEUN) {
         // Heun's trapezoid on the probability-flow ODE (dmip_device.h HeunStep): the Euler stage, then the same
         // network evaluation at x~ and step i + 1's coefficients; no draw
         static_assert(MODE != SAMPLER_CDIFFE && !NOISE, "Heun: CDE and Posterior, x0 from p.x0 or the RNG");
@@ -779,10 +804,15 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
       float* dst = p.xfer + slot * XW;
 #pragma unroll
       for (int k = 0; k < D; ++k) dst[k * 64 + lane] = x[k];
-      dst[(D + 0) * 64 + lane] = __uint_as_float(rng.s0);
-      dst[(D + 1) * 64 + lane] = __uint_as_float(rng.s1);
-      dst[(D + 2) * 64 + lane] = __uint_as_float(rng.s2);
-      dst[(D + 3) * 64 + lane] = __uint_as_float(rng.s3);
+      if constexpr (SOLVER == SOLVER_TABLE) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) dst[(D + k) * 64 + lane] = hist.d[k];
+      } else {
+        dst[(D + 0) * 64 + lane] = __uint_as_float(rng.s0);
+        dst[(D + 1) * 64 + lane] = __uint_as_float(rng.s1);
+        dst[(D + 2) * 64 + lane] = __uint_as_float(rng.s2);
+        dst[(D + 3) * 64 + lane] = __uint_as_float(rng.s3);
+      }
       handover_publish(p.xflag + slot, lane, p.debug_flags);
     } else if (const long long cn = chain_now(); sg.kind != 3 && sg.job >= 0 && cn < p.n_chains && g == 0) {
       float* dst = p.x_out + ((size_t)yi * p.n_chains + cn) * D;
@@ -834,5 +864,8 @@ hipError_t launch_x3_sampler_cdiffe(const X3SamplerParams& p, int width, int xdi
 // the Heun (probability-flow ODE) instantiations of the one-tile engine (dmip_x3_{cde,post}_heun.hip)
 hipError_t launch_x3_sampler_cde_heun(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_x3_sampler_post_heun(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+// the table-driven multistep (DPM-Solver++(2M) / DDIM) instantiations (dmip_x3_{cde,post}_ms.hip)
+hipError_t launch_x3_sampler_cde_ms(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+hipError_t launch_x3_sampler_post_ms(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 
 }  // namespace dmip

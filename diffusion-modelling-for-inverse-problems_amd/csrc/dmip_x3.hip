@@ -3,7 +3,11 @@
 // dmip_x3_{cde,post,cdiffe}.hip so they compile in parallel.
 #include "dmip_x3.h"
 
+#include "../../include/dmip.h"
+
 namespace dmip {
+static_assert(kSolverTable == SOLVER_TABLE, "the host layer's name of SOLVER_TABLE");
+static_assert(kMultistepCols == DMIP_MULTISTEP_COLS, "the step table's row (dmip_device.h MultistepStep)");
 namespace x3 {
 
 // CDE / likelihood layer-1 bias with y folded in: c (b1_u + W1_{u,y} . y), f64 accumulation, one
@@ -55,6 +59,11 @@ hipError_t launch_x3_sampler(const X3SamplerParams& p, int mode, int width, int 
     if (mode == SAMPLER_CDE) return launch_x3_sampler_cde_heun(p, width, xdim, n_y, st, supported);
     return launch_x3_sampler_post_heun(p, width, xdim, n_y, st, supported);
   }
+  if (p.solver == SOLVER_TABLE) {
+    if (!x3_multistep_supported(mode, width, n_hidden, xdim)) return hipSuccess;
+    if (mode == SAMPLER_CDE) return launch_x3_sampler_cde_ms(p, width, xdim, n_y, st, supported);
+    return launch_x3_sampler_post_ms(p, width, xdim, n_y, st, supported);
+  }
   if (mode == SAMPLER_CDE) return launch_x3_sampler_cde(p, width, xdim, n_y, st, supported);
   if (mode == SAMPLER_POSTERIOR) return launch_x3_sampler_post(p, width, xdim, n_y, st, supported);
   return launch_x3_sampler_cdiffe(p, width, xdim, ydim, n_y, st, supported);
@@ -75,6 +84,11 @@ bool x3_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim)
 // them free of scratch, W = 512 included: DESIGN.md 3e)
 bool x3_heun_supported(int mode, int width, int n_hidden, int xdim) {
   return (mode == SAMPLER_CDE || mode == SAMPLER_POSTERIOR) && x3_sampler_supported(mode, width, n_hidden, xdim, 0);
+}
+
+// The table-driven multistep sampler (dmip_device.h MultistepStep): the shapes of the Heun units
+bool x3_multistep_supported(int mode, int width, int n_hidden, int xdim) {
+  return x3_heun_supported(mode, width, n_hidden, xdim);
 }
 
 }  // namespace dmip

@@ -14,6 +14,9 @@ CDE and PosteriorDiffusionEstimator sample the whole lambda family of the refere
 (dmip_flow_logp, exact f32); `model.sample_with_log_prob(y, n)` draws samples of that ODE together with their
 log-density in one launch (dmip_flow_sample, exact f32). Both take `precision="fp32x3"` for the same scheme on the
 split-fp16 engine (dmip_flow_logp_ex / dmip_flow_sample_ex); their default is exact f32 whatever `model.precision` is.
+`solver="heun"` samples that ODE with second-order steps (dmip_ode_sample); `solver="dpm2m"` (DPM-Solver++(2M)) and
+`"ddim"` with one network evaluation per step on a grid uniform in the log-SNR (dmip_multistep_sample, from the step
+table of `multistep_table`).
 Precision (`model.precision`, or `precision=` per call; default from $DMIP_PRECISION, else "fp32x3"):
   "fp32x3" -- the reference's fp32 arithmetic at the fp16 matrix rate: every product as three fp16 MFMAs
              (W_hi h_hi + W_hi h_lo + W_lo h_hi, fp32 accumulation; csrc/dmip_x3.h), tanh by exp2 + rcp.
@@ -83,11 +86,25 @@ def _check_lmbd(lmbd, model):
     return lmbd
 
 
-def _check_solver(solver, lmbd, model, x0=None, noise=None):
+def _check_solver(solver, lmbd, model, x0=None, noise=None, grid="logsnr", t_end=None):
     """The effective lmbd of a sampling call. solver="heun" is the second-order sampler of the probability-flow ODE
     (dmip_ode_sample): lmbd left at its default or given as 1.0, CDE and PosteriorDiffusionEstimator only, no noise
-    to inject. x0= (the chains' start states) needs it."""
-    _lib.solver_code(solver)
+    to inject. x0= (the chains' start states) needs it, or one of the few-step solvers "dpm2m" / "ddim"
+    (dmip_multistep_sample), which integrate the same ODE under the same rules and alone take grid= and t_end=."""
+    if solver in _lib.TABLE_SOLVERS:
+        if not isinstance(model, (CDE, PosteriorDiffusionEstimator)):
+            raise ValueError(f"{type(model).__name__}: solver='{solver}' is implemented for CDE and "
+                             "PosteriorDiffusionEstimator only")
+        if float(lmbd) not in (0.0, 1.0):
+            raise ValueError(f"solver='{solver}' integrates the probability-flow ODE (lmbd = 1), got lmbd={lmbd}")
+        if noise is not None:
+            raise ValueError(f"solver='{solver}' draws no noise per step: pass the start states as x0=, not noise=")
+        _check_grid(grid, t_end, float(model.sde.T))
+        return 1.0
+    if solver not in _lib.SOLVERS:
+        raise ValueError(f"solver must be one of {sorted(_lib.SOLVERS) + list(_lib.TABLE_SOLVERS)}, got {solver!r}")
+    if grid != "logsnr" or t_end is not None:
+        raise ValueError("grid= and t_end= belong to solver='dpm2m' / 'ddim' (the other samplers run the uniform grid)")
     if solver == "heun":
         if not isinstance(model, (CDE, PosteriorDiffusionEstimator)):
             raise ValueError(f"{type(model).__name__}: solver='heun' is implemented for CDE and "
@@ -101,6 +118,67 @@ def _check_solver(solver, lmbd, model, x0=None, noise=None):
         raise ValueError("x0= needs solver='heun'; the Euler samplers take their start states through the noise= "
                          "argument (slot 0 of the injected normals)")
     return _check_lmbd(lmbd, model)
+
+
+MULTISTEP_GRIDS = ("logsnr", "uniform")
+
+
+def _check_grid(grid, t_end, T):
+    """t_end of a few-step sampling call as a float: None is 1e-3 T; 0 < t_end < T."""
+    if grid not in MULTISTEP_GRIDS:
+        raise ValueError(f"grid must be one of {MULTISTEP_GRIDS}, got {grid!r}")
+    t_end = 1e-3 * T if t_end is None else float(t_end)
+    if not 0.0 < t_end < T:
+        raise ValueError(f"t_end must be in (0, T = {T}), got {t_end}")
+    return t_end
+
+
+def multistep_table(solver, grid, num_steps, beta_min, beta_max, T, t_end=None):
+    """The step table of dmip_multistep_sample in float64, (num_steps, 8): row i is tau_i | p_i q_i | cx_i c0_i c1_i |
+    g_i | 0 with d = p x + q a and x' = cx x + c0 d + c1 d_prev (include/dmip.h), for solver "dpm2m"
+    (DPM-Solver++(2M)) or "ddim" (c1 = 0) of the VP-SDE (beta_min, beta_max, T) on
+      grid "logsnr"   tau_0 = T .. tau_{S-1} = t_end uniform in the log-SNR lambda = log(alpha / sigma), then 0 (lambda
+                      inverts in closed form for the linear beta schedule); t_end defaults to 1e-3 T
+      grid "uniform"  the samplers' own f32 grid tau_i = T - T linspace(0, 1, S + 1)[i], whose last step reaches 0
+                      (t_end is checked and unused).
+    The times are rounded to the f32 the network sees first and every coefficient is formed from those, so the table
+    and the network agree on tau. num_steps is the number of network evaluations; the last step, to sigma = 0, returns
+    the denoised estimate and is first order for both solvers."""
+    if solver not in _lib.TABLE_SOLVERS:
+        raise ValueError(f"solver must be one of {_lib.TABLE_SOLVERS}, got {solver!r}")
+    S, T = int(num_steps), float(T)
+    bmin, bd = float(beta_min), float(beta_max) - float(beta_min)
+    t_end = _check_grid(grid, t_end, T)
+    if S < 1:
+        raise ValueError("num_steps must be >= 1")
+    B = lambda t: 0.5 * t * t * bd + t * bmin                      # the integral of beta: alpha = exp(-B / 2)
+    lam = lambda t: -0.5 * B(t) - 0.5 * np.log(-np.expm1(-B(t)))   # log(alpha / sigma)
+    if grid == "uniform":
+        Tf = torch.tensor(T, dtype=torch.float32)
+        tau = (Tf - torch.linspace(0, 1, S + 1, dtype=torch.float32) * Tf)[:S].double().numpy()  # the kernels' step_coef
+    else:
+        lams = np.linspace(lam(T), lam(t_end), S) if S > 1 else np.array([lam(T)])
+        Bl = np.logaddexp(0.0, -2.0 * lams)                        # alpha^2 = 1 / (1 + exp(-2 lambda))
+        tau = 2.0 * Bl / (bmin + np.sqrt(bmin * bmin + 2.0 * bd * Bl))
+        tau[0] = T
+        if S > 1:
+            tau[-1] = t_end
+        tau = tau.astype(np.float32).astype(np.float64)
+    if not (np.all(np.diff(tau) < 0) and tau[-1] > 0):
+        raise ValueError(f"multistep_table: the grid's f32 times are not strictly decreasing to t_end = {t_end} "
+                         f"(num_steps = {S} is too many for this grid)")
+    alpha, sigma2 = np.exp(-0.5 * B(tau)), -np.expm1(-B(tau))
+    sigma, lm, g = np.sqrt(sigma2), lam(tau), np.sqrt(bmin + bd * tau)
+    tab = np.zeros((S, _lib.DMIP_MULTISTEP_COLS))
+    tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 6] = tau, 1.0 / alpha, sigma2 / (g * alpha), g
+    h = np.diff(lm)                                                # h_i = lambda_{i+1} - lambda_i > 0, i < S - 1
+    E = -alpha[1:] * np.expm1(-h)
+    tab[:-1, 3], tab[:-1, 4] = sigma[1:] / sigma[:-1], E
+    if solver == "dpm2m" and S > 2:
+        w = 0.5 * h[1:] / h[:-1]                                   # 1 / (2 r_i), r_i = h_{i-1} / h_i, i = 1 .. S - 2
+        tab[1:-1, 4], tab[1:-1, 5] = E[1:] * (1.0 + w), -E[1:] * w
+    tab[-1, 3:6] = 0.0, 1.0, 0.0                                   # x_S = d_{S-1}
+    return tab
 
 
 def _x0_tensor(x0, ys, num_samples, xdim, dev):
@@ -121,15 +199,20 @@ def _fused_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DM
     one that is compiled (_MORE_ACCURATE); None when none is (per-step loop). `acts`: the networks' activation
     chains -- a SiLU network has the exact-f32 CDE sampler only (include/dmip.h dmip_act), and its Heun kernel at
     every shape of that sampler. solver="heun": fp32x3 (the one-tile engine) or fp32; "fp16" runs fp32x3 (there is
-    no 16-bit Heun kernel)."""
+    no 16-bit Heun kernel); "dpm2m" / "ddim" likewise (dmip_multistep_supported)."""
     _lib.precision_code(precision)
     precision = canonical_precision(precision)
     if any(a != _lib.DMIP_ACT_TANH_TWICE_FIRST for a in acts):
         ok = mode == _lib.DMIP_SAMPLER_CDE and _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, "fp32")
         return "fp32" if ok else None
     for prec in (precision,) + _MORE_ACCURATE[precision]:
-        if _lib.ode_sample_supported(width, n_hidden, xdim, ydim, mode, prec) if solver == "heun" else \
-                _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, prec):
+        if solver in _lib.TABLE_SOLVERS:
+            ok = _lib.multistep_supported(width, n_hidden, xdim, ydim, mode, prec)
+        elif solver == "heun":
+            ok = _lib.ode_sample_supported(width, n_hidden, xdim, ydim, mode, prec)
+        else:
+            ok = _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, prec)
+        if ok:
             return prec
     return None
 
@@ -158,10 +241,14 @@ def _flow_hint(precision):
 
 
 def _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec,
-                  lmbd=0.0, solver="euler", x0=None, noise=None):
-    """The fused CDE / Posterior launch of sample_device: dmip_ode_sample for Heun, dmip_em_sample_lmbd for
-    lmbd != 0, else the reverse SDE's own entry point (dmip_em_sample / dmip_em_sample_posterior)."""
-    if solver == "heun":
+                  lmbd=0.0, solver="euler", x0=None, noise=None, table=None):
+    """The fused CDE / Posterior launch of sample_device: dmip_multistep_sample for "dpm2m" / "ddim" (`table`: their
+    step table on the device), dmip_ode_sample for Heun, dmip_em_sample_lmbd for lmbd != 0, else the reverse SDE's own
+    entry point (dmip_em_sample / dmip_em_sample_posterior)."""
+    if solver in _lib.TABLE_SOLVERS:
+        _lib.multistep_sample(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed, out,
+                              x0, precision=prec)
+    elif solver == "heun":
         _lib.ode_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, "heun",
                         x0, precision=prec)
     elif lmbd != 0.0:
@@ -188,33 +275,40 @@ class BaseClassDiffusionModel:
 
     # ----------------------------------------------------------------- sampling API
     def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, precision=None, lmbd=0.0,
-                solver="euler"):
+                solver="euler", grid="logsnr", t_end=None):
         """Posterior samples for one observation y (ydim,): np.ndarray (num_samples, xdim) float32
         (models/diffusion.py:27-46). Under torch.distributed with world_size > 1 the chains are
         sharded over the ranks and every rank returns all num_samples (parallel.sample_sharded).
         `precision` overrides self.precision for this call; `lmbd` in [0, 1] selects the reverse process of
         sdes.py:77-87 (0: the reverse SDE, 1: the deterministic probability-flow ODE; CDE and Posterior only).
         `solver="heun"` samples that ODE with Heun's second-order steps (two network evaluations per step; about
-        an eighth of the Euler steps reach the same accuracy: DESIGN.md 3e), sharded like every other call."""
+        an eighth of the Euler steps reach the same accuracy: DESIGN.md 3e), sharded like every other call.
+        `solver="dpm2m"` (DPM-Solver++(2M)) and `"ddim"` sample it with one evaluation per step on a grid uniform in
+        the log-SNR (`grid="logsnr"`, ending at `t_end`, default 1e-3 T, before the last step to 0; `grid="uniform"`
+        is the other samplers' grid): num_steps is then the number of evaluations."""
         from . import parallel
-        lmbd = _check_solver(solver, lmbd, self)
+        lmbd = _check_solver(solver, lmbd, self, grid=grid, t_end=t_end)
         # (sample_sharded's launch is guarded: the device status word was read after it, so an asynchronous kernel
         # failure has raised already rather than coming back as silent NaNs)
         kw = {"lmbd": lmbd} if lmbd != 0.0 else {}
         if solver != "euler":
             kw["solver"] = solver
+        if solver in _lib.TABLE_SOLVERS:
+            kw.update(grid=grid, t_end=t_end)
         x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std, precision=precision, **kw)
         return x.cpu().numpy()
 
     def sample_trajectory(self, y, num_samples=2000, num_steps=200, snapshot_every=10, mean=0, std=1, seed=None,
-                          chain_offset=0, precision=None, corrector_steps=0, snr=0.16, lmbd=0.0, solver="euler"):
+                          chain_offset=0, precision=None, corrector_steps=0, snr=0.16, lmbd=0.0, solver="euler",
+                          grid="logsnr", t_end=None):
         """The fused sampler with trajectory snapshots (dmip_em_sample_snapshots): returns device tensors
         (x (n_y, num_samples, xdim), snaps (num_steps // snapshot_every, n_y, num_samples, xdim)), snaps[k]
         = the chains after step (k + 1) * snapshot_every of the loop of models/diffusion.py:27-46 (the
         reference returns only the final state). Same chains, RNG and sharding as sample_device; `lmbd` as
         forward (dmip_em_sample_lmbd with snapshots); `solver="heun"`: the states after each full Heun step
-        (dmip_ode_sample)."""
-        lmbd = _check_solver(solver, lmbd, self)
+        (dmip_ode_sample); `solver="dpm2m"` / `"ddim"` with `grid` and `t_end` as forward: the states after each of
+        their steps (dmip_multistep_sample)."""
+        lmbd = _check_solver(solver, lmbd, self, grid=grid, t_end=t_end)
         nets, mode = _nets_and_mode(self, NotImplementedError(f"{type(self).__name__}: no fused trajectory sampler"),
                                     cdiffe=True)
         if corrector_steps and mode != _lib.DMIP_SAMPLER_CDIFFE:
@@ -231,6 +325,13 @@ class BaseClassDiffusionModel:
         snaps = torch.empty(int(num_steps) // int(snapshot_every), ys.shape[0], int(num_samples), self.xdim,
                             device=dev, dtype=torch.float32)
         seed = _draw_seed() if seed is None else seed
+        if solver in _lib.TABLE_SOLVERS:
+            if not 1 <= int(snapshot_every) <= int(num_steps):
+                raise ValueError("snapshot_every must be in [1, num_steps]")
+            table = self._multistep_table(solver, grid, num_steps, t_end, dev)
+            _lib.multistep_sample(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed,
+                                  out, None, snapshot_every, snaps, prec)
+            return out, snaps
         if solver == "heun":
             if not 1 <= int(snapshot_every) <= int(num_steps):
                 raise ValueError("snapshot_every must be in [1, num_steps]")
@@ -336,6 +437,12 @@ class BaseClassDiffusionModel:
                                                        mean, std, seed, out, logq, x0, precision))
         return (out[0], logq[0]) if single else (out, logq)
 
+    def _multistep_table(self, solver, grid, num_steps, t_end, dev):
+        """multistep_table of this model's VP-SDE as the kernels read it: rounded once to f32, on `dev`."""
+        base = self.sde.base_sde
+        tab = multistep_table(solver, grid, num_steps, base.beta_min, base.beta_max, self.sde.T, t_end)
+        return torch.from_numpy(tab).to(torch.float32).to(dev).contiguous()
+
     def _exec_device(self, y):
         if isinstance(y, torch.Tensor) and y.is_cuda:
             return y.device
@@ -352,7 +459,7 @@ class BaseClassDiffusionModel:
         return ys.reshape(-1, self.ydim).contiguous()
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None):
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None):
         """Device-resident samples (n_y, num_samples, xdim) for ys (n_y, ydim) -- no host copy.
         `chain_offset` selects a shard of a larger run; `noise` injects standard normals
         (num_steps + 1, n_y, num_samples, xdim) (slot 0 -> x0) in place of the internal RNG;
@@ -362,7 +469,10 @@ class BaseClassDiffusionModel:
         (dmip_ode_sample; fp32x3 on the one-tile engine, or fp32; "fp16" runs fp32x3), from the same x0 as the Euler
         samplers at the same seed -- or from `x0` (n_y, num_samples, xdim) ((num_samples, xdim) for one y; with
         chain_offset the rows of this shard), e.g. the latent of log_prob(..., return_latent=True): the two are an
-        encode / decode pair."""
+        encode / decode pair.
+        `solver="dpm2m"` / `"ddim"` (CDE and Posterior): the few-step samplers of that ODE from a step table
+        (dmip_multistep_sample; multistep_table), num_steps network evaluations on `grid` ("logsnr", ending at `t_end`,
+        or "uniform"); x0, seed, chain_offset and precision as for "heun"."""
         raise NotImplementedError
 
     def _prepare(self, y, num_samples, num_steps, nets):
@@ -426,8 +536,8 @@ class CDE(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None):
-        lmbd = _check_solver(solver, lmbd, self, x0, noise)
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None):
+        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end)
         net = self.sde.a
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [net])
         handle = net.dmip_handle(dev, self.xdim)
@@ -447,10 +557,15 @@ class CDE(BaseClassDiffusionModel):
             def drift(x, y, tvec):
                 return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
 
+            if solver in _lib.TABLE_SOLVERS:
+                return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0,
+                                              self._multistep_table(solver, grid, num_steps, t_end, dev),
+                                              lambda x, y, tvec, g: self.sde.a(x, y, tvec))
             return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
                                    drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
+        table = self._multistep_table(solver, grid, num_steps, t_end, dev) if solver in _lib.TABLE_SOLVERS else None
         return _fused_launch(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps, mean,
-                             std, seed, out, prec, lmbd, solver, x0, noise)
+                             std, seed, out, prec, lmbd, solver, x0, noise, table)
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         from .training import DeviceTrainStep, _plain_adam, device_step_enabled, device_step_ok, fused_config, \
@@ -529,6 +644,28 @@ def _em_device_loop(model, ys, num_samples, num_steps, mean, std, seed, chain_of
                 z = z_in + delta * mu + delta ** 0.5 * sigma * xi
                 x = z[:, :keep] if keep < z.shape[1] else z
             outs.append(x[:, :keep])
+    return torch.stack(outs)
+
+
+def _multistep_device_loop(model, ys, num_samples, seed, chain_offset, mean, std, x0, table, score):
+    """solver="dpm2m" / "ddim" for shapes without a compiled fused sampler: the update of csrc/dmip_device.h
+    MultistepStep from the same f32 table (num_steps, 8) on the device, in its rounding order (f32 tensor ops, no
+    fusion), one network launch (dmip_mlp_forward) per network and step. score(x, y, tvec, g) is a (CDE) or
+    g (likelihood + prior) (Posterior). The start states are _em_device_loop's: the loop's own chain-keyed x0, or x0."""
+    dev = ys.device
+    rows = table.cpu()
+    outs = []
+    with torch.no_grad():
+        for k in range(ys.shape[0]):
+            x = x0[k] if x0 is not None else \
+                _loop_normals(seed, int(chain_offset), _LOOP_STREAM + (k << 40), num_samples, model.xdim, dev) * std + mean
+            d_prev = torch.zeros_like(x)
+            for tau, p, q, cx, c0, c1, g, _ in rows.tolist():
+                a = score(x, ys[k], torch.full((num_samples, 1), tau, device=dev), g)
+                d = p * x + q * a
+                x = (cx * x + c0 * d) + c1 * d_prev
+                d_prev = d
+            outs.append(x)
     return torch.stack(outs)
 
 
@@ -626,8 +763,8 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         self.loss_fn = PosteriorLoss
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None):
-        lmbd = _check_solver(solver, lmbd, self, x0, noise)
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None):
+        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         score = self.sde.a
@@ -640,9 +777,14 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         if (prior.width, prior.n_hidden) == (lik.width, lik.n_hidden):
             prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width, lik.n_hidden,
                                     self.xdim, self.ydim, [prior.act, lik.act], solver)
+        table = self._multistep_table(solver, grid, num_steps, t_end, dev) if solver in _lib.TABLE_SOLVERS else None
         if prec is not None:
             return _fused_launch(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset,
-                                 num_steps, mean, std, seed, out, prec, lmbd, solver, x0)
+                                 num_steps, mean, std, seed, out, prec, lmbd, solver, x0, table=table)
+        if table is not None:  # a = g (likelihood + prior) at the table's g, as the fused kernel forms it
+            return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0, table,
+                                          lambda x, y, tvec, g: g * (score.likelihood_net(x, y, tvec) +
+                                                                     score.prior_net(x, tvec)))
         base = self.sde.base_sde
 
         def drift(x, y, tvec):

@@ -216,6 +216,36 @@ int dmip_ode_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const 
                     float* snap_out_dev, float* x_out_dev, void* stream);
 int dmip_ode_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision, int solver);
 
+/* Few-step sampling along the probability-flow ODE from a step table: DPM-Solver++(2M) (Lu et al. 2022) and its
+ * first-order case DDIM, in data-prediction form, one network evaluation per step and no noise. On a decreasing grid
+ * tau_0 = T > ... > tau_{S-1} > tau_S = 0 with alpha_i, sigma_i the VP mean weight and std at tau_i, lambda_i =
+ * log(alpha_i / sigma_i), h_i = lambda_{i+1} - lambda_i, g_i = sqrt(beta(tau_i)) and a = g score:
+ *   d_i     = (x_i + (sigma_i^2 / g_i) a_i) / alpha_i
+ *   x_{i+1} = (sigma_{i+1} / sigma_i) x_i - alpha_{i+1} expm1(-h_i) D_i,     x_S = d_{S-1}
+ *   D_i     = d_i (DDIM; 2M at i = 0), or (1 + 1/(2r)) d_i - (1/(2r)) d_{i-1} with r = h_{i-1} / h_i (2M)
+ * The kernels know the table, not the scheme that built it: row i of table_dev [num_steps][DMIP_MULTISTEP_COLS] is
+ *   tau_i | p_i q_i | cx_i c0_i c1_i | g_i | 0
+ * and a step is a = net(x, y, tau_i) (a = g_i (likelihood + prior) for DMIP_SAMPLER_POSTERIOR), then, every operation
+ * rounded to f32 and none fused,
+ *   d = p_i x + q_i a;   x <- (cx_i x + c0_i d) + c1_i d_prev;   d_prev <- d         (d_prev = 0 before step 0)
+ * so DDIM is the same kernel at c1 = 0, and a non-default VP-SDE or another grid enters through the table alone (the
+ * Python package builds it in float64: estimators.multistep_table; the grid uniform in lambda is the one on which the
+ * second order shows). num_steps is the number of network evaluations.
+ *   x0_dev, chain_offset, seed, mean, stdv, snapshot_every / snap_out_dev: as dmip_ode_sample at DMIP_SOLVER_HEUN (the
+ *   same x0 at the same seed; shards of a run are bit-identical to the whole run, a tile handed from one wave to the
+ *   next carries d_prev with it).
+ * precision: DMIP_PREC_F32 or DMIP_PREC_F32X3 (the one-tile engine); DMIP_PREC_FP16 is DMIP_ERR_UNSUPPORTED (there is
+ * no 16-bit kernel), as are a SiLU network except for the exact-f32 CDE sampler and a shape without a kernel
+ * (dmip_multistep_supported: the shapes of dmip_ode_sample_supported at DMIP_SOLVER_HEUN). Modes other than CDE /
+ * Posterior, table_cols != DMIP_MULTISTEP_COLS, num_steps < 1, a bad snapshot_every and null arguments (the table
+ * included) are DMIP_ERR_INVALID, checked in that order; every argument is validated before any device work. */
+#define DMIP_MULTISTEP_COLS 8
+int dmip_multistep_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev, int n_y, int ydim,
+                          int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, const float* table_dev,
+                          int table_cols, float mean, float stdv, uint64_t seed, int precision, const float* x0_dev,
+                          int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream);
+int dmip_multistep_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision);
+
 /* Samples of the probability-flow ODE together with their model log-density, exact f32, one launch: the steps of
  * dmip_ode_sample's DMIP_SOLVER_HEUN at DMIP_PREC_F32 (same grid, same m, same f32 rounding order, same x0: x_out is
  * that sampler's x_out) and, beside them, the divergence of the drift from forward tangents through the network
