@@ -6,12 +6,15 @@ ARCH ?= gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-parameter
 F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(CSRC)/dmip_f32_cdiffe.o $(CSRC)/dmip_flow.o \
            $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o \
-           $(CSRC)/dmip_dps_linear.o $(CSRC)/dmip_f32_cde_ms.o $(CSRC)/dmip_f32_post_ms.o
+           $(CSRC)/dmip_dps_linear.o $(CSRC)/dmip_f32_cde_ms.o $(CSRC)/dmip_f32_post_ms.o \
+           $(CSRC)/dmip_flow_pairs.o $(CSRC)/dmip_flow_sample_pairs.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o \
           $(CSRC)/dmip_x3_flow.o $(CSRC)/dmip_x3_flow_cde.o $(CSRC)/dmip_x3_flow_post.o \
           $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o $(CSRC)/dmip_x3_dps_linear.o \
-          $(CSRC)/dmip_x3_cde_ms.o $(CSRC)/dmip_x3_post_ms.o
+          $(CSRC)/dmip_x3_cde_ms.o $(CSRC)/dmip_x3_post_ms.o \
+          $(CSRC)/dmip_x3_flow_pairs.o $(CSRC)/dmip_x3_flow_pairs_cde.o $(CSRC)/dmip_x3_flow_pairs_post.o \
+          $(CSRC)/dmip_x3_flow_sample_pairs_cde.o $(CSRC)/dmip_x3_flow_sample_pairs_post.o
 # the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, training entry points) and
 # the weight packers (pure host code, dmip_pack.h)
 CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train dmip_capi_dps_linear dmip_pack
@@ -63,6 +66,11 @@ $(CSRC)/dmip_flow_sample.o: $(CSRC)/dmip_flow_sample.hip $(CSRC)/dmip_flow.h $(C
 $(CSRC)/dmip_dps_linear.o: $(CSRC)/dmip_dps_linear.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# the paired flow kernels (one observation per row), exact f32: dmip_flow.h's network with a per-row layer-1 bias
+PAIRSHDRS := $(CSRC)/dmip_pairs.h $(CSRC)/dmip_flow_rows.h $(HDRS)
+$(CSRC)/dmip_flow_pairs.o $(CSRC)/dmip_flow_sample_pairs.o: $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/dmip_flow_pairs.h $(CSRC)/dmip_flow.h $(CSRC)/dmip_f32.h $(PAIRSHDRS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # fp32-accurate split-fp16 engine (DMIP_PREC_F32X3): one header, four translation units; no SLP
 # vectorisation (it packs the split's f32 subtractions into v_pk_add_f32, an anti-lever beside MFMAs)
 $(CSRC)/dmip_x3.o: $(CSRC)/dmip_x3.hip $(CSRC)/dmip_x3.h $(HDRS)
@@ -79,6 +87,15 @@ $(CSRC)/dmip_x3_flow.o: $(CSRC)/dmip_x3_flow.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/
 $(CSRC)/dmip_x3_flow_%.o: $(CSRC)/dmip_x3_flow_%.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
+# the paired flow kernels on the fp32x3 engine: the dispatch and four translation units of instantiations (static
+# pattern rules: they beat dmip_x3_flow_%.o)
+$(CSRC)/dmip_x3_flow_pairs.o: $(CSRC)/dmip_x3_flow_pairs.hip $(PAIRSHDRS)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+X3PAIRS := dmip_x3_flow_pairs_cde dmip_x3_flow_pairs_post dmip_x3_flow_sample_pairs_cde dmip_x3_flow_sample_pairs_post
+$(patsubst %,$(CSRC)/%.o,$(X3PAIRS)): $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/dmip_x3_flow_pairs.h $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_x3.h $(PAIRSHDRS)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
 # the same on the fp32x3 engine (listed before nothing else matches it: an explicit rule beats dmip_x3_%.o)
 $(CSRC)/dmip_x3_dps_linear.o: $(CSRC)/dmip_x3_dps_linear.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
@@ -91,7 +108,7 @@ $(CSRC)/dmip_x3k.o: $(CSRC)/dmip_x3k.hip $(CSRC)/dmip_x3k.h $(CSRC)/dmip_x3.h $(
 $(CSRC)/dmip_dps_x3.o: $(CSRC)/dmip_dps_x3.hip $(CSRC)/dmip_mh_chains.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
-CAPIHDRS := $(CSRC)/dmip_capi_common.h $(CSRC)/dmip_pack.h $(HDRS)
+CAPIHDRS := $(CSRC)/dmip_capi_common.h $(CSRC)/dmip_pack.h $(CSRC)/dmip_pairs.h $(HDRS)
 $(CAPIOBJS): $(CSRC)/%.o: $(CSRC)/%.cpp $(CAPIHDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

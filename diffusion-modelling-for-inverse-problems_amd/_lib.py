@@ -44,7 +44,8 @@ EXPORTED = (
     "dmip_ode_sample", "dmip_ode_sample_supported", "dmip_flow_sample", "dmip_flow_sample_supported",
     "dmip_flow_logp_ex", "dmip_flow_sample_ex", "dmip_flow_logp_supported_precision",
     "dmip_flow_sample_supported_precision", "dmip_mala_sample", "dmip_dps_linear_supported", "dmip_dps_linear_sample",
-    "dmip_multistep_sample", "dmip_multistep_supported",
+    "dmip_multistep_sample", "dmip_multistep_supported", "dmip_flow_pairs_supported", "dmip_flow_logp_pairs",
+    "dmip_flow_sample_pairs",
 )
 DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
 SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
@@ -157,6 +158,13 @@ def _declare(lib):
                                             _c_void_p, _i32, _c_void_p]
         lib.dmip_flow_logp_supported_precision.argtypes = [_i32] * 6
         lib.dmip_flow_sample_supported_precision.argtypes = [_i32] * 6
+    if hasattr(lib, "dmip_flow_logp_pairs"):  # (absent from older builds loaded by A/B timing scripts)
+        lib.dmip_flow_pairs_supported.argtypes = [_i32] * 6
+        lib.dmip_flow_logp_pairs.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p,
+                                             _i32, _i32, _i64, _i32, _c_void_p, _c_void_p, _i32, _c_void_p]
+        lib.dmip_flow_sample_pairs.argtypes = [_i32, _c_void_p, _c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _i32,
+                                               _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _c_void_p, _c_void_p,
+                                               _c_void_p, _i32, _c_void_p]
     if hasattr(lib, "dmip_train_plan_create"):
         lib.dmip_train_plan_create.argtypes = [ctypes.POINTER(DmipTrainPlanDesc), ctypes.POINTER(_c_void_p)]
         lib.dmip_train_plan_step.argtypes = [_c_void_p, _c_void_p, _c_void_p, _c_void_p]
@@ -494,6 +502,34 @@ def flow_sample(mode, net, prior, sde, y, n_chains, chain_offset, num_steps, mea
     check(lib().dmip_flow_sample_ex(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), n_y, ydim, net.xdim,
                                     int(n_chains), int(chain_offset), int(num_steps), float(mean), float(std),
                                     _u64(seed), ptr(x0), ptr(out), ptr(logq), code, stream_of(y.device)))
+
+
+def flow_pairs_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32"):
+    """flow_logp_supported's answer for the paired entry points (dmip_flow_logp_pairs, dmip_flow_sample_pairs)."""
+    return bool(lib().dmip_flow_pairs_supported(precision_code(precision), mode, width, n_hidden, xdim, ydim))
+
+
+def flow_logp_pairs(mode, net, prior, sde, x, y, num_steps, logp, latent=None, precision="fp32"):
+    """dmip_flow_logp_pairs: log p(x_i | y_i) of x (n, xdim) under y (n, ydim), one observation per row, into logp
+    (n,) [and x_S into latent (n, xdim)]."""
+    calls["flow_logp_pairs"] += 1
+    _status_pending.add(_dev_index(y.device))  # (parallel.guarded then reads the status word after the launch)
+    n, ydim = y.shape
+    check(lib().dmip_flow_logp_pairs(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(x), ptr(y), ydim, net.xdim,
+                                     int(n), int(num_steps), ptr(logp), ptr(latent), precision_code(precision),
+                                     stream_of(y.device)))
+
+
+def flow_sample_pairs(mode, net, prior, sde, y, chain_offset, num_steps, mean, std, seed, out, logq, x0=None,
+                      precision="fp32"):
+    """dmip_flow_sample_pairs: one Heun sample of the probability-flow ODE per row of y (n, ydim) into out (n, xdim)
+    with its log-density into logq (n,); x0 (n, xdim) replaces the rows' own start states."""
+    calls["flow_sample_pairs"] += 1
+    _status_pending.add(_dev_index(y.device))  # (parallel.guarded then reads the status word after the launch)
+    n, ydim = y.shape
+    check(lib().dmip_flow_sample_pairs(int(mode), net.h, _h(prior), ctypes.byref(sde), ptr(y), ydim, net.xdim, int(n),
+                                       int(chain_offset), int(num_steps), float(mean), float(std), _u64(seed), ptr(x0),
+                                       ptr(out), ptr(logq), precision_code(precision), stream_of(y.device)))
 
 
 def sampler_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp16"):

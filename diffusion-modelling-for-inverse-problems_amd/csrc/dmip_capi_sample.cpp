@@ -2,6 +2,7 @@
 // probability-flow log-likelihood, the surrogate's forward / log-posterior, MH and DPS, the RNG and schedule probes,
 // and the *_supported queries. Argument validation first, then stream-ordered launches.
 #include "dmip_capi_common.h"
+#include "dmip_pairs.h"
 
 using namespace dmip_capi;
 
@@ -676,6 +677,147 @@ int flow_sample_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const
   return e == hipSuccess ? DMIP_OK : hip_fail(e, "flow_sample launch");
 }
 
+// ---- the paired entry points: one observation per row (dmip_pairs.h)
+// rows per slab: the [rows][W] layer-1 bias scratch stays within 32 MiB (test hook, not ABI: DMIP_PAIRS_SLAB_ROWS=k
+// forces k rows per slab). Rows are independent, so the slabs of a call give the bits of one launch
+int64_t pairs_slab_rows(int width) {
+  if (const char* e = getenv("DMIP_PAIRS_SLAB_ROWS")) {
+    const long long v = atoll(e);
+    if (v >= 1) return (int64_t)v;
+  }
+  return (int64_t)((32u << 20) / ((size_t)width * sizeof(float)));
+}
+// (the kernels index the scratch with 32-bit offsets: a forced slab stays below 2^31 floats)
+int64_t pairs_slab_bound(int64_t slab, int width) { return std::min<int64_t>(slab, ((int64_t)1 << 31) / width - 1); }
+
+// what both paired entry points check after their own arguments: the networks, the activation chain, the shape
+int pairs_check(const char* who, int mode, const dmip_mlp* net, const dmip_mlp* net1, const dmip_vpsde* sde, int ydim,
+                int xdim, int64_t n, int64_t offset, bool rows, int num_steps, bool x3) {
+  if (int rc = check_nets(who, net, net1, xdim, xdim, ydim, 1, rows, n, offset, num_steps, sde)) return rc;
+  if (f32_act(net) || (net1 && f32_act(net1)))
+    return fail(DMIP_ERR_UNSUPPORTED, std::string(who) + ": the tanh chain only (no SiLU kernel)");
+  if (!(x3 ? dmip::x3_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)
+           : dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)))
+    return no_kernel("paired flow kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
+  return x3 ? x3_flow_check("paired flow kernel", mode, net, net1, xdim) : DMIP_OK;
+}
+
+// a slab's layer-1 biases c_i (and, exact f32, the shared zero-bias layer-1 image) on the stream
+int pairs_prep(StreamScratch& bias, StreamScratch& l1, const dmip_mlp* net, const float* y_dev, int64_t rows, int xdim,
+               int ydim, bool x3, hipStream_t st) {
+  const int k1q = (xdim + 2 + 3) / 4;
+  if (int rc = bias.alloc((size_t)rows * net->width * sizeof(float), st)) return rc;
+  if (!x3)
+    if (int rc = l1.alloc((size_t)(net->width / 16) * k1q * 64 * sizeof(float), st)) return rc;
+  dmip::PairsPrepParams pp{net->w1, net->b1, y_dev, (float*)bias.ptr, (float*)l1.ptr, rows, net->width, net->in_dim,
+                           xdim, ydim, k1q, x3 ? (double)dmip::kPairsTanhScale : 1.0};
+  const hipError_t e = dmip::launch_pairs_prep(pp, st);
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "paired layer-1 bias prep launch");
+}
+
+int flow_logp_pairs_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                         const float* x_dev, const float* y_dev, int ydim, int xdim, int64_t n, int num_steps,
+                         float* logp_out_dev, float* latent_out_dev, int precision, void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "flow_logp_pairs: CDE and Posterior estimators only");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (n < 1) return fail(DMIP_ERR_INVALID, "n must be >= 1");
+  if (!net || !sde || !x_dev || !y_dev || !logp_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
+    return fail(DMIP_ERR_INVALID, "null argument");
+  if (int rc = check_flow_precision(precision)) return rc;
+  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
+  const bool x3 = precision != DMIP_PREC_F32;
+  if (int rc = pairs_check("flow_logp_pairs", mode, net, net1, sde, ydim, xdim, n, 0, true, num_steps, x3)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t slab = pairs_slab_bound(pairs_slab_rows(net->width), net->width);
+  for (int64_t r0 = 0; r0 < n; r0 += slab) {
+    const int64_t rows = std::min<int64_t>(slab, n - r0);
+    StreamScratch bias, l1;
+    if (int rc = pairs_prep(bias, l1, net, y_dev + (size_t)r0 * ydim, rows, xdim, ydim, x3, st)) return rc;
+    const dmip::FlowRows fr = fill_rows(*sde, x_dev + (size_t)r0 * xdim, logp_out_dev + r0,
+                                        latent_out_dev ? latent_out_dev + (size_t)r0 * xdim : nullptr, rows, num_steps);
+    bool ok = false;
+    hipError_t e;
+    if (x3) {
+      dmip::X3FlowPairsParams p{};
+      p.x.net[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
+      if (net1) p.x.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
+      p.x.n_hidden = net->n_hidden;
+      p.x.bias_y = p.row_bias = (const float*)bias.ptr;
+      p.x.rows = fr;
+      p.x.err = status_word(dmip::stream_device(st));
+      if (!p.x.err) return fail(DMIP_ERR_ALLOC, "device status word");
+      e = dmip::launch_x3_flow_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
+    } else {
+      dmip::F32FlowPairsParams p{};
+      p.f.net[0] = f32_net(net);
+      if (net1) p.f.net[1] = f32_net(net1);
+      p.f.n_hidden = net->n_hidden;
+      p.f.l1y = (const float*)l1.ptr;
+      p.row_bias = (const float*)bias.ptr;
+      p.f.rows = fr;
+      e = dmip::launch_f32_flow_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
+    }
+    if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled paired log-likelihood kernel");
+    if (e != hipSuccess) return hip_fail(e, "flow_logp_pairs launch");
+  }
+  return DMIP_OK;
+}
+
+int flow_sample_pairs_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                           const float* y_dev, int ydim, int xdim, int64_t n, int64_t chain_offset, int num_steps,
+                           float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
+                           float* logq_out_dev, int precision, void* stream) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
+    return fail(DMIP_ERR_INVALID, "flow_sample_pairs: CDE and Posterior estimators only");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (n < 1) return fail(DMIP_ERR_INVALID, "n must be >= 1");
+  if (!(stdv > 0.0f)) return fail(DMIP_ERR_INVALID, "stdv must be > 0");
+  if (!net || !sde || !y_dev || !x_out_dev || !logq_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
+    return fail(DMIP_ERR_INVALID, "null argument");
+  if (int rc = check_flow_precision(precision)) return rc;
+  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
+  const bool x3 = precision != DMIP_PREC_F32;
+  if (int rc = pairs_check("flow_sample_pairs", mode, net, net1, sde, ydim, xdim, n, chain_offset, false, num_steps,
+                           x3))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t slab = pairs_slab_bound(pairs_slab_rows(net->width), net->width);
+  for (int64_t r0 = 0; r0 < n; r0 += slab) {
+    const int64_t rows = std::min<int64_t>(slab, n - r0);
+    StreamScratch bias, l1;
+    if (int rc = pairs_prep(bias, l1, net, y_dev + (size_t)r0 * ydim, rows, xdim, ydim, x3, st)) return rc;
+    const dmip::FlowChains fc =
+        fill_chains(*sde, xdim, rows, chain_offset + r0, num_steps, mean, stdv, seed,
+                    x0_dev ? x0_dev + (size_t)r0 * xdim : nullptr, x_out_dev + (size_t)r0 * xdim, logq_out_dev + r0);
+    bool ok = false;
+    hipError_t e;
+    if (x3) {
+      dmip::X3FlowSamplePairsParams p{};
+      p.x.net[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
+      if (net1) p.x.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
+      p.x.n_hidden = net->n_hidden;
+      p.x.bias_y = p.row_bias = (const float*)bias.ptr;
+      p.x.chains = fc;
+      p.x.err = status_word(dmip::stream_device(st));
+      if (!p.x.err) return fail(DMIP_ERR_ALLOC, "device status word");
+      e = dmip::launch_x3_flow_sample_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
+    } else {
+      dmip::F32FlowSamplePairsParams p{};
+      p.f.net[0] = f32_net(net);
+      if (net1) p.f.net[1] = f32_net(net1);
+      p.f.n_hidden = net->n_hidden;
+      p.f.l1y = (const float*)l1.ptr;
+      p.row_bias = (const float*)bias.ptr;
+      p.f.chains = fc;
+      e = dmip::launch_f32_flow_sample_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
+    }
+    if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled paired flow_sample kernel");
+    if (e != hipSuccess) return hip_fail(e, "flow_sample_pairs launch");
+  }
+  return DMIP_OK;
+}
+
 // the tanh chain's answer, as dmip_sampler_supported_precision's
 int flow_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
   if (precision == DMIP_PREC_F32) return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
@@ -732,6 +874,25 @@ int dmip_flow_sample_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, co
                         float* logq_out_dev, int precision, void* stream) {
   return flow_sample_impl(mode, net, prior, sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv,
                           seed, x0_dev, x_out_dev, logq_out_dev, precision, stream);
+}
+
+int dmip_flow_pairs_supported(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
+  return flow_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
+}
+
+int dmip_flow_logp_pairs(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                         const float* x_dev, const float* y_dev, int ydim, int xdim, int64_t n, int num_steps,
+                         float* logp_out_dev, float* latent_out_dev, int precision, void* stream) {
+  return flow_logp_pairs_impl(mode, net, prior, sde, x_dev, y_dev, ydim, xdim, n, num_steps, logp_out_dev,
+                              latent_out_dev, precision, stream);
+}
+
+int dmip_flow_sample_pairs(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                           const float* y_dev, int ydim, int xdim, int64_t n, int64_t chain_offset, int num_steps,
+                           float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
+                           float* logq_out_dev, int precision, void* stream) {
+  return flow_sample_pairs_impl(mode, net, prior, sde, y_dev, ydim, xdim, n, chain_offset, num_steps, mean, stdv, seed,
+                                x0_dev, x_out_dev, logq_out_dev, precision, stream);
 }
 
 }  // extern "C"

@@ -437,6 +437,86 @@ class BaseClassDiffusionModel:
                                                        mean, std, seed, out, logq, x0, precision))
         return (out[0], logq[0]) if single else (out, logq)
 
+    def _pairs_check(self, who, precision):
+        """What log_prob_pairs and sample_with_log_prob_pairs refuse before any device work (their per-y siblings'
+        refusals): (nets, mode, precision)."""
+        nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: {who} is implemented for CDE and "
+                                                     "PosteriorDiffusionEstimator only"))
+        precision = _flow_precision(precision)
+        layers = [list(n.hidden_layers) for n in nets]
+        widths = set(w for hl in layers for w in hl)
+        if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
+                not _lib.flow_pairs_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
+            raise ValueError(f"{who}: no compiled paired kernel for hidden layers {layers}, xdim {self.xdim}"
+                             + _flow_hint(precision))
+        if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
+            raise ValueError(f"{who}: the kernel computes the tanh chain only")
+        return nets, mode, precision
+
+    def _pairs_y(self, who, y):
+        y = torch.as_tensor(y)
+        if y.ndim != 2 or y.shape[1] != self.ydim or y.shape[0] < 1:
+            raise ValueError(f"{who}: y must be (n, ydim) with n >= 1, one observation per row")
+        return y
+
+    def log_prob_pairs(self, x, y, num_steps=200, return_latent=False, precision=None):
+        """log p(x_i | y_i) for n pairs, one observation per row: x (n, xdim), y (n, ydim) -> a float32 device tensor
+        (n,); return_latent=True: (logp, x_S (n, xdim)). The scheme, precisions and refusals of log_prob; what
+        log_prob(x[:, None, :], y)[:, 0] computes, in one launch over all rows instead of one workgroup per pair
+        (dmip_flow_logp_pairs): y enters through a per-row layer-1 bias. A row's value does not depend on n or on the
+        row's position. Single-device: shard by slicing rows. CDE and PosteriorDiffusionEstimator."""
+        nets, mode, precision = self._pairs_check("log_prob_pairs", precision)
+        x, y = torch.as_tensor(x), self._pairs_y("log_prob_pairs", y)
+        if x.ndim != 2 or x.shape[1] != self.xdim:
+            raise ValueError("log_prob_pairs: x must be (n, xdim)")
+        if x.shape[0] != y.shape[0]:
+            raise ValueError(f"log_prob_pairs: x has {x.shape[0]} rows and y has {y.shape[0]}: one y per row of x")
+        if int(num_steps) < 1:
+            raise ValueError("log_prob_pairs: num_steps must be >= 1")
+        from . import parallel
+        dev = x.device if x.is_cuda else self._exec_device(y)
+        dev, ys, sde, _ = self._prepare(y.to(dev), 0, num_steps, nets)
+        xs = x.to(device=dev, dtype=torch.float32).contiguous()
+        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
+        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        logp = torch.empty(xs.shape[0], device=dev, dtype=torch.float32)
+        latent = torch.empty_like(xs) if return_latent else None
+        # guarded: the device status word is read after the launch
+        parallel.guarded(dev, lambda: _lib.flow_logp_pairs(mode, net, prior, sde, xs, ys, num_steps, logp, latent,
+                                                           precision))
+        return (logp, latent) if return_latent else logp
+
+    def sample_with_log_prob_pairs(self, y, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, x0=None,
+                                   precision=None):
+        """One draw x_i ~ q(. | y_i) per observation with its log-density: y (n, ydim) -> device tensors (x (n, xdim),
+        logq (n,)), in one launch over all rows (dmip_flow_sample_pairs). The scheme, precisions and refusals of
+        sample_with_log_prob. Row i draws its start from stream (seed, chain_offset + i, 0), the start of
+        sample_with_log_prob(y[i], 1, seed=seed, chain_offset=chain_offset + i); x0 (n, xdim) replaces the starts.
+        Shards of a run (rows sliced, chain_offset advanced) are bit-identical to the whole run. Single-device. CDE
+        and PosteriorDiffusionEstimator."""
+        nets, mode, precision = self._pairs_check("sample_with_log_prob_pairs", precision)
+        y = self._pairs_y("sample_with_log_prob_pairs", y)
+        n = int(y.shape[0])
+        if x0 is not None and tuple(torch.as_tensor(x0).shape) != (n, self.xdim):
+            raise ValueError("sample_with_log_prob_pairs: x0 must have shape (n, xdim), one start per row of y")
+        if int(num_steps) < 1:
+            raise ValueError("sample_with_log_prob_pairs: num_steps must be >= 1")
+        if not float(std) > 0.0:
+            raise ValueError(f"sample_with_log_prob_pairs: std must be > 0, got {std}")
+        from . import parallel
+        dev, ys, sde, _ = self._prepare(y, 0, num_steps, nets)
+        if x0 is not None:
+            x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32).contiguous()
+        handles = [m.dmip_handle(dev, self.xdim) for m in nets]
+        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        out = torch.empty(n, self.xdim, device=dev, dtype=torch.float32)
+        logq = torch.empty(n, device=dev, dtype=torch.float32)
+        seed = _draw_seed() if seed is None else seed
+        # guarded: the device status word is read after the launch
+        parallel.guarded(dev, lambda: _lib.flow_sample_pairs(mode, net, prior, sde, ys, chain_offset, num_steps, mean,
+                                                             std, seed, out, logq, x0, precision))
+        return out, logq
+
     def _multistep_table(self, solver, grid, num_steps, t_end, dev):
         """multistep_table of this model's VP-SDE as the kernels read it: rounded once to f32, on `dev`."""
         base = self.sde.base_sde

@@ -211,3 +211,50 @@ def importance_posterior(model, y, log_target_fn, num_samples=4096, num_steps=20
     r = xs - m
     rep.update(x=x, logq=logq, mean=xs.mean(axis=0), snis_mean=m, snis_cov=(w[:, None] * r).T @ r)
     return rep
+
+
+# --------------------------------------------------------------------------- paired workloads: one observation per row
+DEFAULT_LEVELS = tuple(i / 20 for i in range(1, 20))  # credibility levels 0.05 .. 0.95
+
+
+def held_out_log_prob(model, x, y, num_steps=200, precision=None):
+    """Held-out conditional negative log-likelihood of a test set of pairs, x (n, xdim) and y (n, ydim): the
+    model-selection number that needs no MCMC ground truth. One model.log_prob_pairs call; the sums in float64 on the
+    host. Returns {"nll": -mean log p(x_i | y_i), "stderr": its standard error (the sample standard deviation, n - 1,
+    over sqrt(n); 0.0 for n = 1), "n": n}."""
+    lp = _f64(model.log_prob_pairs(x, y, num_steps=num_steps, precision=precision)).reshape(-1)
+    n = lp.shape[0]
+    mean = lp.sum() / n
+    var = ((lp - mean) ** 2).sum() / (n - 1) if n > 1 else 0.0
+    return {"nll": float(-mean), "stderr": float(np.sqrt(var / n)), "n": int(n)}
+
+
+def coverage_from_logq(logq_truth, logq_samples, levels=DEFAULT_LEVELS):
+    """Expected coverage of highest-posterior-density regions from log-densities alone (a pure host function, float64).
+    logq_truth (n,): log q(x_true_i | y_i); logq_samples (n, L): log q of L samples of q(. | y_i). alpha_i is the
+    fraction of row i's samples whose log q exceeds the truth's: the credibility level of the smallest HPD region of
+    q(. | y_i) that holds x_true_i. The expected coverage at a level is mean(alpha_i <= level); for a calibrated q,
+    alpha is uniform on (0, 1) and coverage equals level. Returns {"alpha": (n,), "levels": (k,), "coverage": (k,)}."""
+    lt, ls = _f64(logq_truth).reshape(-1), _f64(logq_samples)
+    if ls.ndim != 2 or ls.shape[0] != lt.shape[0] or ls.shape[1] < 1:
+        raise ValueError("coverage_from_logq: logq_truth must be (n,) and logq_samples (n, L)")
+    lv = np.asarray(levels, np.float64).reshape(-1)
+    alpha = (ls > lt[:, None]).sum(axis=1) / ls.shape[1]
+    return {"alpha": alpha, "levels": lv, "coverage": (alpha[:, None] <= lv[None, :]).mean(axis=0)}
+
+
+def hpd_coverage(model, x_true, y, num_samples, num_steps=200, levels=DEFAULT_LEVELS, seed=None, precision=None):
+    """Calibration of an amortised estimator over simulated pairs x_true (n, xdim), y (n, ydim): num_samples draws of
+    q(. | y_i) with their log q per observation (model.sample_with_log_prob, the multi-y path: many rows per y is what
+    it is built for), log q(x_true_i | y_i) by model.log_prob_pairs, both at the same step count and precision, then
+    coverage_from_logq. (The samples' log q is integrated along their own reverse trajectory and the truths' along the
+    forward grid: they agree to second order in 1 / num_steps.) Returns coverage_from_logq's dict plus logq_truth (n,)
+    and logq_samples (n, num_samples), device tensors."""
+    y = torch.as_tensor(y)
+    if y.ndim != 2:
+        raise ValueError("hpd_coverage: y must be (n, ydim), one observation per row of x_true")
+    _, logq_s = model.sample_with_log_prob(y, num_samples, num_steps=num_steps, seed=seed, precision=precision)
+    logq_t = model.log_prob_pairs(x_true, y, num_steps=num_steps, precision=precision)
+    rep = coverage_from_logq(logq_t, logq_s, levels)
+    rep.update(logq_truth=logq_t, logq_samples=logq_s)
+    return rep

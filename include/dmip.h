@@ -288,6 +288,32 @@ int dmip_flow_sample_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, co
 int dmip_flow_logp_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim);
 int dmip_flow_sample_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim);
 
+/* Paired log-density and sampling: one observation per row (additive entry points, ABI 9). Row i has its own y_i:
+ *   dmip_flow_logp_pairs    logp_out[i] = log p(x_i | y_i) (and latent_out[i] = its x_S, or null) for x [n][xdim],
+ *                           y [n][ydim]: dmip_flow_logp_ex's scheme, row by row
+ *   dmip_flow_sample_pairs  x_out[i] ~ q(. | y_i) with logq_out[i] = log q(x_out[i] | y_i) for y [n][ydim]:
+ *                           dmip_flow_sample_ex's scheme. Row i starts at mean + stdv n with n the first normals of
+ *                           stream (seed, chain_offset + i, 0) -- the start of dmip_flow_sample_ex(y_i, n_chains = 1,
+ *                           chain_offset = chain_offset + i) -- or at row i of x0_dev [n][xdim] when that is given.
+ * One launch sequence for all rows instead of one workgroup per pair: y enters the network only through layer 1's
+ * b1 + W1_y y_i, formed once per row in f64 (rounded once) into stream-ordered scratch and taken as the initial value
+ * of layer 1's accumulator. The scratch is bounded: large n runs in slabs of rows, and since rows are independent the
+ * slabs give the bits of one launch; a row's values do not depend on n or on its position. Single-device; a caller
+ * shards by slicing rows (and chain_offset). precision as dmip_flow_logp_ex, the fp32x3 range handling included (y
+ * never enters the split). Validation before any device work, with dmip_flow_logp_ex's codes: DMIP_ERR_INVALID for a
+ * mode other than CDE / Posterior, num_steps < 1, n < 1, stdv <= 0, a null pointer, an unknown precision, a network
+ * that does not match xdim / ydim; DMIP_ERR_UNSUPPORTED for a SiLU network, prior and likelihood of different hidden
+ * layers, or a shape without a kernel. Shapes: dmip_flow_pairs_supported, the answer of
+ * dmip_flow_logp_supported_precision. */
+int dmip_flow_pairs_supported(int precision, int mode, int width, int n_hidden, int xdim, int ydim);
+int dmip_flow_logp_pairs(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                         const float* x_dev, const float* y_dev, int ydim, int xdim, int64_t n, int num_steps,
+                         float* logp_out_dev, float* latent_out_dev, int precision, void* stream);
+int dmip_flow_sample_pairs(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
+                           const float* y_dev, int ydim, int xdim, int64_t n, int64_t chain_offset, int num_steps,
+                           float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
+                           float* logq_out_dev, int precision, void* stream);
+
 /* ---- training: fused loss value + parameter gradients ----------------------------------------- */
 typedef enum { DMIP_LOSS_DSM = 0, DMIP_LOSS_DSM_PDE = 1, DMIP_LOSS_PINN = 2, DMIP_LOSS_PINN2 = 3 } dmip_loss_kind;
 typedef enum { DMIP_PDE_NONE = 0, DMIP_PDE_FPE = 1, DMIP_PDE_CFPE = 2 } dmip_pde_kind;
