@@ -7,12 +7,13 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall 
 F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(CSRC)/dmip_f32_cdiffe.o $(CSRC)/dmip_flow.o \
            $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o \
            $(CSRC)/dmip_dps_linear.o $(CSRC)/dmip_f32_cde_ms.o $(CSRC)/dmip_f32_post_ms.o \
+           $(CSRC)/dmip_f32_cde_ms_sde.o $(CSRC)/dmip_f32_post_ms_sde.o \
            $(CSRC)/dmip_flow_pairs.o $(CSRC)/dmip_flow_sample_pairs.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o \
           $(CSRC)/dmip_x3_flow.o $(CSRC)/dmip_x3_flow_cde.o $(CSRC)/dmip_x3_flow_post.o \
           $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o $(CSRC)/dmip_x3_dps_linear.o \
-          $(CSRC)/dmip_x3_cde_ms.o $(CSRC)/dmip_x3_post_ms.o \
+          $(CSRC)/dmip_x3_cde_ms.o $(CSRC)/dmip_x3_post_ms.o $(CSRC)/dmip_x3_cde_ms_sde.o $(CSRC)/dmip_x3_post_ms_sde.o \
           $(CSRC)/dmip_x3_flow_pairs.o $(CSRC)/dmip_x3_flow_pairs_cde.o $(CSRC)/dmip_x3_flow_pairs_post.o \
           $(CSRC)/dmip_x3_flow_sample_pairs_cde.o $(CSRC)/dmip_x3_flow_sample_pairs_post.o
 # the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, training entry points) and

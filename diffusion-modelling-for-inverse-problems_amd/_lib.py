@@ -45,12 +45,13 @@ EXPORTED = (
     "dmip_flow_logp_ex", "dmip_flow_sample_ex", "dmip_flow_logp_supported_precision",
     "dmip_flow_sample_supported_precision", "dmip_mala_sample", "dmip_dps_linear_supported", "dmip_dps_linear_sample",
     "dmip_multistep_sample", "dmip_multistep_supported", "dmip_flow_pairs_supported", "dmip_flow_logp_pairs",
-    "dmip_flow_sample_pairs",
+    "dmip_flow_sample_pairs", "dmip_multistep_sde_sample", "dmip_multistep_sde_supported",
 )
 DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
 SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
 # the table-driven few-step samplers of the probability-flow ODE (dmip_multistep_sample): Python-side names, not values
-# of dmip_solver. A row of their step table: tau | p q | cx c0 c1 | g | 0 (include/dmip.h)
+# of dmip_solver. A row of their step table: tau | p q | cx c0 c1 | g | cn (include/dmip.h; cn, the noise coefficient,
+# is read by dmip_multistep_sde_sample alone)
 TABLE_SOLVERS = ("dpm2m", "ddim")
 DMIP_MULTISTEP_COLS = 8
 DMIP_DPS_NLL, DMIP_DPS_NORM = 0, 1
@@ -214,6 +215,11 @@ def _declare(lib):
         lib.dmip_multistep_sample.argtypes = [_i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i64, _i64, _i32,
                                               _c_void_p, _i32, _f32, _f32, _u64t, _i32, _c_void_p, _i32, _c_void_p,
                                               _c_void_p, _c_void_p]
+    if hasattr(lib, "dmip_multistep_sde_sample"):  # additive within ABI 9
+        lib.dmip_multistep_sde_supported.argtypes = [_i32] * 6
+        lib.dmip_multistep_sde_sample.argtypes = [_i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i64, _i64,
+                                                  _i32, _c_void_p, _i32, _f32, _f32, _u64t, _i32, _c_void_p, _i32,
+                                                  _c_void_p, _c_void_p, _c_void_p]
     for name in EXPORTED:  # every entry point returns int but dmip_last_error
         if name != "dmip_last_error" and hasattr(lib, name):
             getattr(lib, name).restype = _i32
@@ -452,6 +458,29 @@ def multistep_sample(mode, net, prior, y, n_chains, chain_offset, num_steps, tab
                                       int(chain_offset), int(num_steps), ptr(table), int(table.shape[1]), float(mean),
                                       float(std), _u64(seed), precision_code(precision), ptr(x0), int(snapshot_every),
                                       ptr(snaps), ptr(out), stream_of(y.device)))
+
+
+def multistep_sde_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32x3"):
+    return bool(lib().dmip_multistep_sde_supported(mode, width, n_hidden, xdim, ydim, precision_code(precision)))
+
+
+def multistep_sde_sample(mode, net, prior, y, n_chains, chain_offset, num_steps, table, mean, std, seed, out, x0=None,
+                         snapshot_every=0, snaps=None, precision="fp32x3"):
+    """dmip_multistep_sde_sample: the fused stochastic few-step sampler (SDE-DPM-Solver++(2M), ancestral / eta-DDIM)
+    from `table` as multistep_sample, whose column 7 is the noise coefficient (estimators.multistep_table(eta=)). A
+    chain draws the Euler sampler's normals: x0's first (consumed also when `x0` replaces the start state), then one
+    set after each step's network evaluation."""
+    if tuple(table.shape) != (int(num_steps), DMIP_MULTISTEP_COLS) or table.dtype != torch.float32 or \
+            not table.is_contiguous() or table.device != y.device:
+        raise ValueError("multistep_sde_sample: table must be a contiguous f32 (num_steps, DMIP_MULTISTEP_COLS) tensor "
+                         "on y's device")
+    calls["multistep_sde_sample"] += 1
+    _status_pending.add(_dev_index(y.device))
+    n_y, ydim = y.shape
+    check(lib().dmip_multistep_sde_sample(int(mode), net.h, _h(prior), ptr(y), n_y, ydim, net.xdim, int(n_chains),
+                                          int(chain_offset), int(num_steps), ptr(table), int(table.shape[1]),
+                                          float(mean), float(std), _u64(seed), precision_code(precision), ptr(x0),
+                                          int(snapshot_every), ptr(snaps), ptr(out), stream_of(y.device)))
 
 
 def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32"):

@@ -44,6 +44,7 @@ struct SampleArgs {
   const float* x0_dev = nullptr;    // Heun: start states [n_y][n_chains][xdim] in place of randn stdv + mean
   // dmip_multistep_sample: the step table [num_steps][kMultistepCols]; its launch is SOLVER_TABLE whatever `solver`
   const float* table_dev = nullptr;
+  bool table_sde = false;           // dmip_multistep_sde_sample: SOLVER_TABLE_SDE (the table's column 7 is read)
 };
 
 // the VP-SDE schedule of a launch: each value evaluated in double and rounded once to the kernels' f32.
@@ -146,7 +147,7 @@ int em_sample_f32(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sa
   }
   if (int rc = fill_common(p, a, st)) return rc;
   p.act = f32_act(net0);
-  p.solver = a.table_dev ? dmip::kSolverTable : a.solver;
+  p.solver = a.table_dev ? (a.table_sde ? dmip::kSolverTableSde : dmip::kSolverTable) : a.solver;
   p.x0 = a.x0_dev;
   p.table = a.table_dev;
   bool ok = false;
@@ -221,7 +222,7 @@ int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sam
   }
   p.bias_y = (float*)bias_y.ptr;
   if (int rc = fill_common(p, a, st)) return rc;
-  p.solver = a.table_dev ? dmip::kSolverTable : a.solver;
+  p.solver = a.table_dev ? (a.table_sde ? dmip::kSolverTableSde : dmip::kSolverTable) : a.solver;
   p.x0 = a.x0_dev;
   p.table = a.table_dev;
   bool ok = false;
@@ -334,7 +335,12 @@ int em_sample_impl(int mode, const dmip_mlp* net0, const dmip_mlp* prior, const 
             ? dmip::f32_heun_supported(mode, net0->width, net0->n_hidden, xdim, f32_act(net0))
             : dmip_ode_sample_supported(mode, net0->width, net0->n_hidden, xdim, ydim, a.precision, a.solver)))
     return no_kernel("Heun sampler", mode, net0, xdim, -1, a.precision);
-  if (a.table_dev &&
+  if (a.table_dev && a.table_sde &&
+      !(a.precision == DMIP_PREC_F32
+            ? dmip::f32_multistep_sde_supported(mode, net0->width, net0->n_hidden, xdim, f32_act(net0))
+            : dmip_multistep_sde_supported(mode, net0->width, net0->n_hidden, xdim, ydim, a.precision)))
+    return no_kernel("stochastic multistep sampler", mode, net0, xdim, -1, a.precision);
+  if (a.table_dev && !a.table_sde &&
       !(a.precision == DMIP_PREC_F32
             ? dmip::f32_multistep_supported(mode, net0->width, net0->n_hidden, xdim, f32_act(net0))
             : dmip_multistep_supported(mode, net0->width, net0->n_hidden, xdim, ydim, a.precision)))
@@ -500,23 +506,36 @@ int dmip_multistep_supported(int mode, int width, int n_hidden, int xdim, int yd
   return 0;
 }
 
-// DPM-Solver++(2M) / DDIM from a step table; every argument is validated before any device work, in dmip_ode_sample's
-// order. The kernels take every time-dependent quantity from the table, so there is no dmip_vpsde here
-int dmip_multistep_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev, int n_y, int ydim,
-                          int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, const float* table_dev,
-                          int table_cols, float mean, float stdv, uint64_t seed, int precision, const float* x0_dev,
-                          int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream) {
+// the stochastic variant's kernels (SOLVER_TABLE_SDE), at the same shapes
+int dmip_multistep_sde_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision) {
+  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR) return 0;
+  if (precision == DMIP_PREC_F32) return dmip::f32_multistep_sde_supported(mode, width, n_hidden, xdim, 0) ? 1 : 0;
+  if (precision == DMIP_PREC_F32X3) return dmip::x3_multistep_sde_supported(mode, width, n_hidden, xdim) ? 1 : 0;
+  return 0;
+}
+
+// DPM-Solver++(2M) / DDIM from a step table (sde: with the noise column and a draw per step); every argument is
+// validated before any device work, in dmip_ode_sample's order. The kernels take every time-dependent quantity from the
+// table, so there is no dmip_vpsde here
+static int multistep_sample_impl(bool sde, int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev,
+                                 int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps,
+                          const float* table_dev, int table_cols, float mean, float stdv, uint64_t seed, int precision,
+                          const float* x0_dev, int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream) {
   if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
-    return fail(DMIP_ERR_INVALID, "multistep_sample: CDE and Posterior samplers only");
+    return fail(DMIP_ERR_INVALID, sde ? "multistep_sde_sample: CDE and Posterior samplers only"
+                                      : "multistep_sample: CDE and Posterior samplers only");
   if (table_cols != DMIP_MULTISTEP_COLS)
-    return fail(DMIP_ERR_INVALID, "multistep_sample: table_cols must be DMIP_MULTISTEP_COLS");
+    return fail(DMIP_ERR_INVALID, sde ? "multistep_sde_sample: table_cols must be DMIP_MULTISTEP_COLS"
+                                      : "multistep_sample: table_cols must be DMIP_MULTISTEP_COLS");
   if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
   if (int rc = check_snapshots(snapshot_every, num_steps, snap_out_dev)) return rc;
   if (!net || !table_dev || !y_dev || !x_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
     return fail(DMIP_ERR_INVALID, "null argument");
   if (precision == DMIP_PREC_FP16)
-    return fail(DMIP_ERR_UNSUPPORTED, "multistep_sample: no 16-bit kernel (DMIP_PREC_F32X3 or DMIP_PREC_F32)");
-  static const dmip_vpsde no_sde{0.0, 0.0, 1.0};  // (the launch's schedule fields are unused by SOLVER_TABLE)
+    return fail(DMIP_ERR_UNSUPPORTED,
+                sde ? "multistep_sde_sample: no 16-bit kernel (DMIP_PREC_F32X3 or DMIP_PREC_F32)"
+                    : "multistep_sample: no 16-bit kernel (DMIP_PREC_F32X3 or DMIP_PREC_F32)");
+  static const dmip_vpsde no_sde{0.0, 0.0, 1.0};  // (the launch's schedule fields are unused by SOLVER_TABLE[_SDE])
   SampleArgs a(&no_sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv, seed, precision,
                x_out_dev, stream);
   a.snap_every = snapshot_every;
@@ -524,7 +543,28 @@ int dmip_multistep_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, 
   a.lmbd = 1.0;
   a.x0_dev = x0_dev;
   a.table_dev = table_dev;
+  a.table_sde = sde;
   return em_sample_impl(mode, net, prior, a);
+}
+
+int dmip_multistep_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev, int n_y, int ydim,
+                          int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, const float* table_dev,
+                          int table_cols, float mean, float stdv, uint64_t seed, int precision, const float* x0_dev,
+                          int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream) {
+  return multistep_sample_impl(false, mode, net, prior, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps,
+                               table_dev, table_cols, mean, stdv, seed, precision, x0_dev, snapshot_every, snap_out_dev,
+                               x_out_dev, stream);
+}
+
+// the stochastic few-step samplers: the same table with column 7 = cn, one draw per step (include/dmip.h)
+int dmip_multistep_sde_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev, int n_y,
+                              int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps,
+                              const float* table_dev, int table_cols, float mean, float stdv, uint64_t seed,
+                              int precision, const float* x0_dev, int snapshot_every, float* snap_out_dev,
+                              float* x_out_dev, void* stream) {
+  return multistep_sample_impl(true, mode, net, prior, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps,
+                               table_dev, table_cols, mean, stdv, seed, precision, x0_dev, snapshot_every, snap_out_dev,
+                               x_out_dev, stream);
 }
 
 int dmip_em_sample_stamps(const dmip_mlp* net, const dmip_vpsde* sde, const float* y_dev, int n_y, int ydim,

@@ -164,8 +164,10 @@ __device__ __forceinline__ float em_update(float x, float a, float xi, const Ste
 // from a buffer), so one seed starts the Euler and the Heun chains from the same x0. For the Posterior estimator
 // a = fl(g_i (lik + prior)) at each stage's own g, as the Euler loop forms it. Both engines (dmip_x3.h,
 // dmip_f32.h) take their arithmetic from here.
-// SOLVER_TABLE (internal: not a value of the C-ABI's dmip_solver) is the table-driven multistep sampler below.
-enum { SOLVER_EULER = 0, SOLVER_HEUN = 1, SOLVER_TABLE = 2 };
+// SOLVER_TABLE (internal: not a value of the C-ABI's dmip_solver) is the table-driven multistep sampler below, and
+// SOLVER_TABLE_SDE its stochastic variant (the same step plus a draw and the table's noise column).
+enum { SOLVER_EULER = 0, SOLVER_HEUN = 1, SOLVER_TABLE = 2, SOLVER_TABLE_SDE = 3 };
+constexpr bool solver_is_table(int solver) { return solver == SOLVER_TABLE || solver == SOLVER_TABLE_SDE; }
 
 struct HeunStep {
   // m(x, i): the drift of em_update at the coefficients c
@@ -197,6 +199,12 @@ struct HeunStep {
 //     x' = fl(fl(fl(cx x) + fl(c0 d)) + fl(c1 d_prev))
 // d_prev starts at 0 (c1 = 0 in row 0), stays in registers, and crosses a hand-over in the slot's RNG words, which
 // are dead after x0 for this solver.
+// SOLVER_TABLE_SDE, the stochastic few-step samplers (SDE-DPM-Solver++(2M), ancestral / eta-DDIM): the same row with
+// column 7 = cn, and one more term, the noise added last:
+//     x' = fl(fl(fl(fl(cx x) + fl(c0 d)) + fl(c1 d_prev)) + fl(cn xi))
+// The chain's stream is the Euler sampler's, draw for draw: the first rng_normals<D> is x0 (drawn and discarded when
+// the caller gives x0), then one rng_normals<D> after each step's network evaluation, the last step's included (there
+// cn = 0). The generator is live, so a hand-over slot is x[D] | rng[4] | d_prev[D] (sampler_xfer_words(2 D)).
 constexpr int kMultistepCols = 8;
 
 struct MultistepStep {
@@ -214,6 +222,15 @@ struct MultistepStep {
   }
   __device__ __forceinline__ float advance(float x, float d, float d_prev) const {
     return __fadd_rn(__fadd_rn(__fmul_rn(cx, x), __fmul_rn(c0, d)), __fmul_rn(c1, d_prev));
+  }
+  // column 7 of row i, cn (SOLVER_TABLE_SDE alone reads it: the deterministic kernels keep the load they had), and
+  // the step with the noise term
+  static __device__ __forceinline__ float load_cn(const float* table, int i) {
+    typedef __attribute__((address_space(4))) const float* const_fptr;
+    return ((const_fptr)(table + (size_t)i * kMultistepCols))[7];
+  }
+  __device__ __forceinline__ float advance_sde(float x, float d, float d_prev, float cn, float xi) const {
+    return __fadd_rn(advance(x, d, d_prev), __fmul_rn(cn, xi));
   }
 };
 

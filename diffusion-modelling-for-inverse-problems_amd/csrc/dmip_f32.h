@@ -313,7 +313,8 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
   const long long tiles_y = (p.n_chains + 15) / 16;
   const long long n_waves = (long long)gridDim.x * NW;  // waves sharing this y
   const long long gw = (long long)blockIdx.x * NW + w;  // this wave among them
-  constexpr int XW = sampler_xfer_words(D);
+  // SOLVER_TABLE_SDE: d_prev[D] behind the live generator's words
+  constexpr int XW = sampler_xfer_words(SOLVER == SOLVER_TABLE_SDE ? 2 * D : D);
   const WaveSchedule sched(tiles_y, S, n_waves, gw);
   const size_t noise_step = (size_t)gridDim.y * p.n_chains * D;
 
@@ -326,7 +327,7 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
     float x[D];
     // SOLVER_TABLE: the previous step's denoised estimate (empty otherwise: a dead array here was enough to shift the
     // other instantiations' register allocation)
-    [[maybe_unused]] MultistepHist<SOLVER == SOLVER_TABLE ? D : 0> hist;
+    [[maybe_unused]] MultistepHist<solver_is_table(SOLVER) ? D : 0> hist;
     bool lost = false;  // the hand-over never arrived: the tile's output is poisoned and reported
     if (sg.kind == 2) {  // resume the tile the previous wave of the grid handed over
       const size_t slot = (size_t)yi * n_waves + gw - 1;
@@ -342,11 +343,25 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
         rng.s1 = __float_as_uint(src[(D + 1) * 64 + lane]);
         rng.s2 = __float_as_uint(src[(D + 2) * 64 + lane]);
         rng.s3 = __float_as_uint(src[(D + 3) * 64 + lane]);
+        if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) hist.d[k] = src[(D + 4 + k) * 64 + lane];
+        }
       }
     } else {
       rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
       float n0[D];
-      if constexpr (SOLVER != SOLVER_EULER) {
+      if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+        // the stream's first draw is x0 whether or not the caller gives one, so the step noise is the same either way
+        rng_normals<D>(rng, n0);
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+        if (p.x0) {
+          const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
+#pragma unroll
+          for (int k = 0; k < D; ++k) x[k] = src[k];
+        }
+      } else if constexpr (SOLVER != SOLVER_EULER) {
         // x0 from the caller's buffer [n_y][n_chains][D], else the first draw of the chain's stream (as Euler's)
         if (p.x0) {
           const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
@@ -375,8 +390,8 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
       const int i = sg.kind == 3 ? 0 : i0;  // idle steps: a dummy tile at step 0, discarded
       // SOLVER_TABLE: the step's row of the host table instead (tau for the network, g for the Posterior's a)
       MultistepStep ms{};
-      if constexpr (SOLVER == SOLVER_TABLE) ms = MultistepStep::load(p.table, i);
-      const StepCoef cf = SOLVER == SOLVER_TABLE ? StepCoef{ms.tau, 0.0f, ms.g, 0.0f, 0.0f}
+      if constexpr (solver_is_table(SOLVER)) ms = MultistepStep::load(p.table, i);
+      const StepCoef cf = solver_is_table(SOLVER) ? StepCoef{ms.tau, 0.0f, ms.g, 0.0f, 0.0f}
                                                  : step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
       float v[C::NV0];
 #pragma unroll
@@ -439,7 +454,22 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
       }
 
       float a[D];
-      if constexpr (SOLVER == SOLVER_TABLE) {
+      if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+        // the stochastic table step (dmip_device.h MultistepStep): the deterministic one, then the chain's next draw
+        // and cn xi added last
+        static_assert(MODE != SAMPLER_CDIFFE && !NOISE && D <= 4, "multistep: CDE and Posterior");
+        score(v, a);
+        const float cn = MultistepStep::load_cn(p.table, i);
+        float xi[D];
+        rng_normals<D>(rng, xi);
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
+          const float d = ms.denoise(x[k], ak);
+          x[k] = ms.advance_sde(x[k], d, hist.d[k], cn, xi[k]);
+          hist.d[k] = d;
+        }
+      } else if constexpr (SOLVER == SOLVER_TABLE) {
         // DPM-Solver++(2M) / DDIM from the table's row (dmip_device.h MultistepStep): one evaluation, no draw
         static_assert(MODE != SAMPLER_CDIFFE && !NOISE && D <= 4, "multistep: CDE and Posterior, d_prev in 4 words");
         score(v, a);
@@ -505,6 +535,10 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, 1) f32_sampler_kernel(F32Sa
         dst[(D + 1) * 64 + lane] = __uint_as_float(rng.s1);
         dst[(D + 2) * 64 + lane] = __uint_as_float(rng.s2);
         dst[(D + 3) * 64 + lane] = __uint_as_float(rng.s3);
+        if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) dst[(D + 4 + k) * 64 + lane] = hist.d[k];
+        }
       }
       handover_publish(p.xflag + slot, lane, p.debug_flags);
     } else if (sg.kind != 3 && valid && g == 0) {
@@ -599,7 +633,7 @@ inline hipError_t launch_f32_sampler_t(const F32SamplerParams& p, int n_y, hipSt
   // capped by the stream device's occupancy above
   F32SamplerParams q = p;
   char* buf = nullptr;
-  hipError_t e = alloc_handover((size_t)g * n_y * NW, D, st, &buf, &q.xfer, &q.xflag);
+  hipError_t e = alloc_handover((size_t)g * n_y * NW, SOLVER == SOLVER_TABLE_SDE ? 2 * D : D, st, &buf, &q.xfer, &q.xflag);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)g, (unsigned)n_y), dim3(NW * 64), 0, st, q);
   e = hipGetLastError();
@@ -646,5 +680,10 @@ hipError_t launch_f32_sampler_post_heun(const F32SamplerParams& p, int width, in
 // the table-driven multistep (DPM-Solver++(2M) / DDIM) instantiations (dmip_f32_{cde,post}_ms.hip)
 hipError_t launch_f32_sampler_cde_ms(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_f32_sampler_post_ms(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+// their stochastic variants (SOLVER_TABLE_SDE; dmip_f32_{cde,post}_ms_sde.hip)
+hipError_t launch_f32_sampler_cde_ms_sde(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st,
+                                          bool* ok);
+hipError_t launch_f32_sampler_post_ms_sde(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st,
+                                           bool* ok);
 
 }  // namespace dmip

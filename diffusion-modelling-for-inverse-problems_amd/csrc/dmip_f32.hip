@@ -41,6 +41,11 @@ hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, in
     if (mode == SAMPLER_CDE) return launch_f32_sampler_cde_heun(p, width, xdim, n_y, st, supported);
     return launch_f32_sampler_post_heun(p, width, xdim, n_y, st, supported);
   }
+  if (p.solver == SOLVER_TABLE_SDE) {
+    if (!f32_multistep_sde_supported(mode, width, n_hidden, xdim, p.act)) return hipSuccess;
+    if (mode == SAMPLER_CDE) return launch_f32_sampler_cde_ms_sde(p, width, xdim, n_y, st, supported);
+    return launch_f32_sampler_post_ms_sde(p, width, xdim, n_y, st, supported);
+  }
   if (p.solver == SOLVER_TABLE) {
     if (!f32_multistep_supported(mode, width, n_hidden, xdim, p.act)) return hipSuccess;
     if (mode == SAMPLER_CDE) return launch_f32_sampler_cde_ms(p, width, xdim, n_y, st, supported);
@@ -75,6 +80,11 @@ bool f32_heun_supported(int mode, int width, int n_hidden, int xdim, int act) {
 // tanh chain would need scratch there too)
 bool f32_multistep_supported(int mode, int width, int n_hidden, int xdim, int act) {
   return f32_heun_supported(mode, width, n_hidden, xdim, act);
+}
+
+// Its stochastic variant (SOLVER_TABLE_SDE): the same shapes, each free of scratch with the draw in
+bool f32_multistep_sde_supported(int mode, int width, int n_hidden, int xdim, int act) {
+  return f32_multistep_supported(mode, width, n_hidden, xdim, act);
 }
 
 // layer-1 k-steps: 2 (in_dim <= 7: every x,t and the linear problem's x,y,t network) or 8 (in_dim

@@ -1,0 +1,25 @@
+// Exact-f32 sampler instantiations: SAMPLER_CDE, the stochastic table-driven multistep sampler (SOLVER_TABLE_SDE:
+// SDE-DPM-Solver++(2M), ancestral / eta-DDIM; dmip_f32.h, dmip_device.h MultistepStep), at the shapes of the
+// deterministic unit dmip_f32_cde_ms.hip: width 512 has the SiLU chain only. Every kernel is free of scratch.
+#include "dmip_f32.h"
+
+namespace dmip {
+
+hipError_t launch_f32_sampler_cde_ms_sde(const F32SamplerParams& p, int width, int xdim, int n_y, hipStream_t st,
+                                           bool* ok) {
+  *ok = true;
+#define X(Wv, Dv)                                                                                   \
+  if (width == Wv && xdim == Dv)                                                                    \
+    return p.act ? launch_f32_sampler_t<SAMPLER_CDE, Wv, Dv, 0, false, 1, SOLVER_TABLE_SDE>(p, n_y, st)  \
+                 : launch_f32_sampler_t<SAMPLER_CDE, Wv, Dv, 0, false, 0, SOLVER_TABLE_SDE>(p, n_y, st);
+#define XS(Wv, Dv)                         \
+  if (width == Wv && xdim == Dv && p.act) \
+    return launch_f32_sampler_t<SAMPLER_CDE, Wv, Dv, 0, false, 1, SOLVER_TABLE_SDE>(p, n_y, st);
+  X(64, 2) X(128, 2) X(256, 2) XS(512, 2) X(64, 3) X(128, 3) X(256, 3) XS(512, 3)
+#undef X
+#undef XS
+  *ok = false;
+  return hipSuccess;
+}
+
+}  // namespace dmip

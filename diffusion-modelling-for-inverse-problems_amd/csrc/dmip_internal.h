@@ -80,6 +80,8 @@ constexpr unsigned kErrRange = 2u;
 // F32SamplerParams / X3SamplerParams::solver of the table-driven multistep sampler, for the host layer (the kernels'
 // SOLVER_TABLE of dmip_device.h; dmip_solver's values name the other two)
 constexpr int kSolverTable = 2;
+// ... and of its stochastic variant (SOLVER_TABLE_SDE: the table's column 7 times a draw, added last)
+constexpr int kSolverTableSde = 3;
 
 // hand-over state of a split tile, per grid wave: x[D] + the xoshiro128** state, one word per lane
 constexpr int sampler_xfer_words(int D) { return (D + 4) * 64; }
@@ -371,6 +373,7 @@ hipError_t launch_f32_sampler(const F32SamplerParams& p, int mode, int width, in
 bool f32_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 bool f32_heun_supported(int mode, int width, int n_hidden, int xdim, int act);
 bool f32_multistep_supported(int mode, int width, int n_hidden, int xdim, int act);
+bool f32_multistep_sde_supported(int mode, int width, int n_hidden, int xdim, int act);
 hipError_t launch_f32_forward(const F32ForwardParams& p, int width, int ot, hipStream_t st, bool* supported);
 hipError_t launch_f32_l1_prep(const F32L1PrepParams& p, int n_y, hipStream_t st);
 
@@ -440,6 +443,7 @@ hipError_t launch_x3_sampler(const X3SamplerParams& p, int mode, int width, int 
 bool x3_sampler_supported(int mode, int width, int n_hidden, int xdim, int ydim);
 bool x3_heun_supported(int mode, int width, int n_hidden, int xdim);
 bool x3_multistep_supported(int mode, int width, int n_hidden, int xdim);
+bool x3_multistep_sde_supported(int mode, int width, int n_hidden, int xdim);
 // the k-major multi-tile engine (dmip_x3k.h): CDE, width 256, 3 hidden layers, xdim 2 or 3
 bool x3k_sampler_supported(int mode, int width, int n_hidden, int xdim);
 hipError_t launch_x3k_sampler(const X3SamplerParams& p, int xdim, int n_y, hipStream_t st, bool* ok);

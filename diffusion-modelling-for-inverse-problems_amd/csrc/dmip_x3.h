@@ -568,6 +568,8 @@ __device__ __forceinline__ void report_range(bool oor, unsigned* err, int lane) 
 // SOLVER_TABLE (CDE and Posterior; dmip_x3_{cde,post}_ms.hip): a step is DPM-Solver++(2M) / DDIM from the row of a host
 // table (dmip_device.h MultistepStep) -- the network once, no draw, d_prev in D registers and, across a hand-over, in
 // the slot's RNG words.
+// SOLVER_TABLE_SDE (dmip_x3_{cde,post}_ms_sde.hip): the same step, then the chain's next draw times the table's column
+// 7, added last; x0's draw is consumed whether or not p.x0 replaces it; the slot is x[D] | rng[4] | d_prev[D].
 template <int MODE, int W, int D, int M, int DIAG = 0>
 struct SamplerCfg {
   static constexpr int NNET = MODE == SAMPLER_POSTERIOR ? 2 : 1;
@@ -625,7 +627,8 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
   const long long tiles_y = (p.n_chains + 15) / 16;
   const long long n_waves = (long long)gridDim.x * NW;  // waves sharing this y
   const long long gw = (long long)blockIdx.x * NW + w;  // this wave among them
-  constexpr int XW = sampler_xfer_words(D);
+  // SOLVER_TABLE_SDE: d_prev[D] behind the live generator's words
+  constexpr int XW = sampler_xfer_words(SOLVER == SOLVER_TABLE_SDE ? 2 * D : D);
   const WaveSchedule sched(tiles_y, S, n_waves, gw);
   const size_t noise_step = (size_t)gridDim.y * p.n_chains * D;
   (void)ST;
@@ -647,7 +650,7 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
     float x[D];
     // SOLVER_TABLE: the previous step's denoised estimate (empty otherwise: a dead array here was enough to shift the
     // other instantiations' register allocation)
-    [[maybe_unused]] MultistepHist<SOLVER == SOLVER_TABLE ? D : 0> hist;
+    [[maybe_unused]] MultistepHist<solver_is_table(SOLVER) ? D : 0> hist;
     if (sg.kind == 2) {  // resume the tile the previous wave of the grid handed over
       const size_t slot = (size_t)yi * n_waves + gw - 1;
       const bool lost = handover_wait(p.xflag + slot, p.spin_limit, p.err, kErrHandover, lane);
@@ -662,11 +665,25 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
         rng.s1 = __float_as_uint(src[(D + 1) * 64 + lane]);
         rng.s2 = __float_as_uint(src[(D + 2) * 64 + lane]);
         rng.s3 = __float_as_uint(src[(D + 3) * 64 + lane]);
+        if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) hist.d[k] = src[(D + 4 + k) * 64 + lane];
+        }
       }
     } else {
       rng = rng_init(p.seed, (uint64_t)(p.chain_offset + c_local), (uint64_t)yi);
       float n0[D];
-      if constexpr (SOLVER != SOLVER_EULER) {
+      if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+        // the stream's first draw is x0 whether or not the caller gives one, so the step noise is the same either way
+        rng_normals<D>(rng, n0);
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = __fadd_rn(__fmul_rn(n0[k], p.stdv), p.mean);
+        if (p.x0) {
+          const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
+#pragma unroll
+          for (int k = 0; k < D; ++k) x[k] = src[k];
+        }
+      } else if constexpr (SOLVER != SOLVER_EULER) {
         // x0 from the caller's buffer [n_y][n_chains][D], else the first draw of the chain's stream (as Euler's)
         if (p.x0) {
           const float* src = p.x0 + ((size_t)yi * p.n_chains + c_rd) * D;
@@ -695,8 +712,8 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
       const int i = sg.kind == 3 ? 0 : i0;  // idle steps: a dummy tile at step 0, discarded
       // SOLVER_TABLE: the step's row of the host table instead (tau for the network, g for the Posterior's a)
       MultistepStep ms{};
-      if constexpr (SOLVER == SOLVER_TABLE) ms = MultistepStep::load(p.table, i);
-      const StepCoef cf = SOLVER == SOLVER_TABLE ? StepCoef{ms.tau, 0.0f, ms.g, 0.0f, 0.0f}
+      if constexpr (solver_is_table(SOLVER)) ms = MultistepStep::load(p.table, i);
+      const StepCoef cf = solver_is_table(SOLVER) ? StepCoef{ms.tau, 0.0f, ms.g, 0.0f, 0.0f}
                                                  : step_coef(i, S, p.T, p.bmin, p.bdiff, p.c_mu, p.c_sig);
       float v[C::NV];
 #pragma unroll
@@ -749,7 +766,21 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
 
       float a[D];
       score(v, a);
-      if constexpr (SOLVER == SOLVER_TABLE) {
+      if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+        // the stochastic table step (dmip_device.h MultistepStep): the deterministic one, then the chain's next draw
+        // and cn xi added last
+        static_assert(MODE != SAMPLER_CDIFFE && !NOISE && D <= 4, "multistep: CDE and Posterior");
+        const float cn = MultistepStep::load_cn(p.table, i);
+        float xi[D];
+        rng_normals<D>(rng, xi);
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const float ak = MODE == SAMPLER_POSTERIOR ? __fmul_rn(cf.g, a[k]) : a[k];
+          const float d = ms.denoise(x[k], ak);
+          x[k] = ms.advance_sde(x[k], d, hist.d[k], cn, xi[k]);
+          hist.d[k] = d;
+        }
+      } else if constexpr (SOLVER == SOLVER_TABLE) {
         // DPM-Solver++(2M) / DDIM from the table's row (dmip_device.h MultistepStep): one evaluation, no draw
         static_assert(MODE != SAMPLER_CDIFFE && !NOISE && D <= 4, "multistep: CDE and Posterior, d_prev in 4 words");
 #pragma unroll
@@ -812,6 +843,10 @@ __global__ void __launch_bounds__(Shape<W>::NW * 64, Shape<W>::NW / 4) x3_sample
         dst[(D + 1) * 64 + lane] = __uint_as_float(rng.s1);
         dst[(D + 2) * 64 + lane] = __uint_as_float(rng.s2);
         dst[(D + 3) * 64 + lane] = __uint_as_float(rng.s3);
+        if constexpr (SOLVER == SOLVER_TABLE_SDE) {
+#pragma unroll
+          for (int k = 0; k < D; ++k) dst[(D + 4 + k) * 64 + lane] = hist.d[k];
+        }
       }
       handover_publish(p.xflag + slot, lane, p.debug_flags);
     } else if (const long long cn = chain_now(); sg.kind != 3 && sg.job >= 0 && cn < p.n_chains && g == 0) {
@@ -840,7 +875,7 @@ inline hipError_t launch_x3_sampler_t(const X3SamplerParams& p, int n_y, hipStre
   // capped by the stream device's occupancy above
   X3SamplerParams q = p;
   char* buf = nullptr;
-  hipError_t e = alloc_handover((size_t)g * n_y * NW, D, st, &buf, &q.xfer, &q.xflag);
+  hipError_t e = alloc_handover((size_t)g * n_y * NW, SOLVER == SOLVER_TABLE_SDE ? 2 * D : D, st, &buf, &q.xfer, &q.xflag);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)g, (unsigned)n_y), dim3(NW * 64), 0, st, q);
   e = hipGetLastError();
@@ -867,5 +902,9 @@ hipError_t launch_x3_sampler_post_heun(const X3SamplerParams& p, int width, int 
 // the table-driven multistep (DPM-Solver++(2M) / DDIM) instantiations (dmip_x3_{cde,post}_ms.hip)
 hipError_t launch_x3_sampler_cde_ms(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_x3_sampler_post_ms(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+// their stochastic variants (SOLVER_TABLE_SDE; dmip_x3_{cde,post}_ms_sde.hip)
+hipError_t launch_x3_sampler_cde_ms_sde(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+hipError_t launch_x3_sampler_post_ms_sde(const X3SamplerParams& p, int width, int xdim, int n_y, hipStream_t st,
+                                          bool* ok);
 
 }  // namespace dmip

@@ -7,6 +7,7 @@
 
 namespace dmip {
 static_assert(kSolverTable == SOLVER_TABLE, "the host layer's name of SOLVER_TABLE");
+static_assert(kSolverTableSde == SOLVER_TABLE_SDE, "the host layer's name of SOLVER_TABLE_SDE");
 static_assert(kMultistepCols == DMIP_MULTISTEP_COLS, "the step table's row (dmip_device.h MultistepStep)");
 namespace x3 {
 
@@ -59,6 +60,11 @@ hipError_t launch_x3_sampler(const X3SamplerParams& p, int mode, int width, int 
     if (mode == SAMPLER_CDE) return launch_x3_sampler_cde_heun(p, width, xdim, n_y, st, supported);
     return launch_x3_sampler_post_heun(p, width, xdim, n_y, st, supported);
   }
+  if (p.solver == SOLVER_TABLE_SDE) {
+    if (!x3_multistep_sde_supported(mode, width, n_hidden, xdim)) return hipSuccess;
+    if (mode == SAMPLER_CDE) return launch_x3_sampler_cde_ms_sde(p, width, xdim, n_y, st, supported);
+    return launch_x3_sampler_post_ms_sde(p, width, xdim, n_y, st, supported);
+  }
   if (p.solver == SOLVER_TABLE) {
     if (!x3_multistep_supported(mode, width, n_hidden, xdim)) return hipSuccess;
     if (mode == SAMPLER_CDE) return launch_x3_sampler_cde_ms(p, width, xdim, n_y, st, supported);
@@ -89,6 +95,11 @@ bool x3_heun_supported(int mode, int width, int n_hidden, int xdim) {
 // The table-driven multistep sampler (dmip_device.h MultistepStep): the shapes of the Heun units
 bool x3_multistep_supported(int mode, int width, int n_hidden, int xdim) {
   return x3_heun_supported(mode, width, n_hidden, xdim);
+}
+
+// Its stochastic variant (SOLVER_TABLE_SDE): the same shapes, each free of scratch with the draw in
+bool x3_multistep_sde_supported(int mode, int width, int n_hidden, int xdim) {
+  return x3_multistep_supported(mode, width, n_hidden, xdim);
 }
 
 }  // namespace dmip

@@ -86,17 +86,35 @@ def _check_lmbd(lmbd, model):
     return lmbd
 
 
-def _check_solver(solver, lmbd, model, x0=None, noise=None, grid="logsnr", t_end=None):
+def _check_eta(eta):
+    """eta of the stochastic few-step samplers as a float: finite and >= 0."""
+    try:
+        eta = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError(f"eta must be a finite float >= 0, got {eta!r}") from None
+    if not (np.isfinite(eta) and eta >= 0.0):
+        raise ValueError(f"eta must be a finite float >= 0, got {eta!r}")
+    return eta
+
+
+def _check_solver(solver, lmbd, model, x0=None, noise=None, grid="logsnr", t_end=None, eta=0.0):
     """The effective lmbd of a sampling call. solver="heun" is the second-order sampler of the probability-flow ODE
     (dmip_ode_sample): lmbd left at its default or given as 1.0, CDE and PosteriorDiffusionEstimator only, no noise
     to inject. x0= (the chains' start states) needs it, or one of the few-step solvers "dpm2m" / "ddim"
-    (dmip_multistep_sample), which integrate the same ODE under the same rules and alone take grid= and t_end=."""
+    (dmip_multistep_sample), which integrate the same ODE under the same rules and alone take grid= and t_end=, and
+    eta= (their stochastic variants, dmip_multistep_sde_sample)."""
+    eta = _check_eta(eta)
+    if eta != 0.0 and solver not in _lib.TABLE_SOLVERS:
+        raise ValueError(f"eta= belongs to solver='dpm2m' / 'ddim', got solver={solver!r}")
     if solver in _lib.TABLE_SOLVERS:
         if not isinstance(model, (CDE, PosteriorDiffusionEstimator)):
             raise ValueError(f"{type(model).__name__}: solver='{solver}' is implemented for CDE and "
                              "PosteriorDiffusionEstimator only")
         if float(lmbd) not in (0.0, 1.0):
             raise ValueError(f"solver='{solver}' integrates the probability-flow ODE (lmbd = 1), got lmbd={lmbd}")
+        if noise is not None and eta != 0.0:
+            raise ValueError(f"solver='{solver}' with eta={eta} draws its step noise from the chain's generator: "
+                             "noise= injection is not implemented for it (start states go in x0=)")
         if noise is not None:
             raise ValueError(f"solver='{solver}' draws no noise per step: pass the start states as x0=, not noise=")
         _check_grid(grid, t_end, float(model.sde.T))
@@ -133,9 +151,9 @@ def _check_grid(grid, t_end, T):
     return t_end
 
 
-def multistep_table(solver, grid, num_steps, beta_min, beta_max, T, t_end=None):
+def multistep_table(solver, grid, num_steps, beta_min, beta_max, T, t_end=None, eta=0.0):
     """The step table of dmip_multistep_sample in float64, (num_steps, 8): row i is tau_i | p_i q_i | cx_i c0_i c1_i |
-    g_i | 0 with d = p x + q a and x' = cx x + c0 d + c1 d_prev (include/dmip.h), for solver "dpm2m"
+    g_i | cn_i with d = p x + q a and x' = cx x + c0 d + c1 d_prev + cn xi (include/dmip.h), for solver "dpm2m"
     (DPM-Solver++(2M)) or "ddim" (c1 = 0) of the VP-SDE (beta_min, beta_max, T) on
       grid "logsnr"   tau_0 = T .. tau_{S-1} = t_end uniform in the log-SNR lambda = log(alpha / sigma), then 0 (lambda
                       inverts in closed form for the linear beta schedule); t_end defaults to 1e-3 T
@@ -143,7 +161,16 @@ def multistep_table(solver, grid, num_steps, beta_min, beta_max, T, t_end=None):
                       (t_end is checked and unused).
     The times are rounded to the f32 the network sees first and every coefficient is formed from those, so the table
     and the network agree on tau. num_steps is the number of network evaluations; the last step, to sigma = 0, returns
-    the denoised estimate and is first order for both solvers."""
+    the denoised estimate and is first order for both solvers.
+    eta >= 0 (finite) selects the stochastic variants (dmip_multistep_sde_sample reads column 7, the deterministic
+    entry point ignores it): for i < S - 1, with h = lambda_{i+1} - lambda_i,
+      cx = (sigma' / sigma) e^{-eta h},  c0 + c1 = -alpha' expm1(-(1 + eta) h),  cn = sigma' sqrt(-expm1(-2 eta h))
+    and c1 = -(c0 + c1) / (2 r) for "dpm2m". eta = 0 is the deterministic table, bit for bit (cn = 0); eta = 1 is
+    SDE-DPM-Solver++(2M) ("dpm2m") and ancestral sampling, the DDIM paper's eta = 1 ("ddim"). Between 0 and 1 this
+    exponent convention (k-diffusion's dpmpp_2m_sde) is the definition, not the DDIM paper's linear eta. For every eta,
+    cx alpha_i + c0 + c1 = alpha_{i+1} and cx^2 sigma_i^2 + cn^2 = sigma_{i+1}^2: a step maps the exact marginal of a
+    point mass to the exact marginal."""
+    eta = _check_eta(eta)
     if solver not in _lib.TABLE_SOLVERS:
         raise ValueError(f"solver must be one of {_lib.TABLE_SOLVERS}, got {solver!r}")
     S, T = int(num_steps), float(T)
@@ -172,12 +199,17 @@ def multistep_table(solver, grid, num_steps, beta_min, beta_max, T, t_end=None):
     tab = np.zeros((S, _lib.DMIP_MULTISTEP_COLS))
     tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 6] = tau, 1.0 / alpha, sigma2 / (g * alpha), g
     h = np.diff(lm)                                                # h_i = lambda_{i+1} - lambda_i > 0, i < S - 1
-    E = -alpha[1:] * np.expm1(-h)
-    tab[:-1, 3], tab[:-1, 4] = sigma[1:] / sigma[:-1], E
+    if eta == 0.0:
+        E = -alpha[1:] * np.expm1(-h)
+        tab[:-1, 3], tab[:-1, 4] = sigma[1:] / sigma[:-1], E
+    else:
+        E = -alpha[1:] * np.expm1(-(1.0 + eta) * h)
+        tab[:-1, 3], tab[:-1, 4] = sigma[1:] / sigma[:-1] * np.exp(-eta * h), E
+        tab[:-1, 7] = sigma[1:] * np.sqrt(-np.expm1(-2.0 * eta * h))
     if solver == "dpm2m" and S > 2:
         w = 0.5 * h[1:] / h[:-1]                                   # 1 / (2 r_i), r_i = h_{i-1} / h_i, i = 1 .. S - 2
         tab[1:-1, 4], tab[1:-1, 5] = E[1:] * (1.0 + w), -E[1:] * w
-    tab[-1, 3:6] = 0.0, 1.0, 0.0                                   # x_S = d_{S-1}
+    tab[-1, 3:6] = 0.0, 1.0, 0.0                                   # x_S = d_{S-1} (and cn = 0)
     return tab
 
 
@@ -194,19 +226,22 @@ def _x0_tensor(x0, ys, num_samples, xdim, dev):
 
 
 def _fused_precision(precision, mode, width, n_hidden, xdim, ydim, acts=(_lib.DMIP_ACT_TANH_TWICE_FIRST,),
-                     solver="euler"):
+                     solver="euler", eta=0.0):
     """The precision a fused kernel runs this shape in: the requested one, else the next more accurate
     one that is compiled (_MORE_ACCURATE); None when none is (per-step loop). `acts`: the networks' activation
     chains -- a SiLU network has the exact-f32 CDE sampler only (include/dmip.h dmip_act), and its Heun kernel at
     every shape of that sampler. solver="heun": fp32x3 (the one-tile engine) or fp32; "fp16" runs fp32x3 (there is
-    no 16-bit Heun kernel); "dpm2m" / "ddim" likewise (dmip_multistep_supported)."""
+    no 16-bit Heun kernel); "dpm2m" / "ddim" likewise (dmip_multistep_supported; dmip_multistep_sde_supported at
+    eta != 0)."""
     _lib.precision_code(precision)
     precision = canonical_precision(precision)
     if any(a != _lib.DMIP_ACT_TANH_TWICE_FIRST for a in acts):
         ok = mode == _lib.DMIP_SAMPLER_CDE and _lib.sampler_supported(width, n_hidden, xdim, ydim, mode, "fp32")
         return "fp32" if ok else None
     for prec in (precision,) + _MORE_ACCURATE[precision]:
-        if solver in _lib.TABLE_SOLVERS:
+        if solver in _lib.TABLE_SOLVERS and eta != 0.0:
+            ok = _lib.multistep_sde_supported(width, n_hidden, xdim, ydim, mode, prec)
+        elif solver in _lib.TABLE_SOLVERS:
             ok = _lib.multistep_supported(width, n_hidden, xdim, ydim, mode, prec)
         elif solver == "heun":
             ok = _lib.ode_sample_supported(width, n_hidden, xdim, ydim, mode, prec)
@@ -241,13 +276,14 @@ def _flow_hint(precision):
 
 
 def _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec,
-                  lmbd=0.0, solver="euler", x0=None, noise=None, table=None):
+                  lmbd=0.0, solver="euler", x0=None, noise=None, table=None, eta=0.0):
     """The fused CDE / Posterior launch of sample_device: dmip_multistep_sample for "dpm2m" / "ddim" (`table`: their
-    step table on the device), dmip_ode_sample for Heun, dmip_em_sample_lmbd for lmbd != 0, else the reverse SDE's own
+    step table on the device; dmip_multistep_sde_sample at eta != 0), dmip_ode_sample for Heun, dmip_em_sample_lmbd for lmbd != 0, else the reverse SDE's own
     entry point (dmip_em_sample / dmip_em_sample_posterior)."""
     if solver in _lib.TABLE_SOLVERS:
-        _lib.multistep_sample(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed, out,
-                              x0, precision=prec)
+        launch = _lib.multistep_sde_sample if eta != 0.0 else _lib.multistep_sample
+        launch(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed, out, x0,
+               precision=prec)
     elif solver == "heun":
         _lib.ode_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, "heun",
                         x0, precision=prec)
@@ -275,7 +311,7 @@ class BaseClassDiffusionModel:
 
     # ----------------------------------------------------------------- sampling API
     def forward(self, y, num_samples=2000, num_steps=200, mean=0, std=1, precision=None, lmbd=0.0,
-                solver="euler", grid="logsnr", t_end=None):
+                solver="euler", grid="logsnr", t_end=None, eta=0.0):
         """Posterior samples for one observation y (ydim,): np.ndarray (num_samples, xdim) float32
         (models/diffusion.py:27-46). Under torch.distributed with world_size > 1 the chains are
         sharded over the ranks and every rank returns all num_samples (parallel.sample_sharded).
@@ -285,9 +321,13 @@ class BaseClassDiffusionModel:
         an eighth of the Euler steps reach the same accuracy: DESIGN.md 3e), sharded like every other call.
         `solver="dpm2m"` (DPM-Solver++(2M)) and `"ddim"` sample it with one evaluation per step on a grid uniform in
         the log-SNR (`grid="logsnr"`, ending at `t_end`, default 1e-3 T, before the last step to 0; `grid="uniform"`
-        is the other samplers' grid): num_steps is then the number of evaluations."""
+        is the other samplers' grid): num_steps is then the number of evaluations.
+        `eta` > 0 with those two solvers draws fresh noise at every step (the stochastic few-step samplers:
+        eta = 1 is SDE-DPM-Solver++(2M) for "dpm2m" and ancestral sampling, the DDIM paper's eta = 1, for "ddim";
+        between 0 and 1 eta is k-diffusion's exponent convention, x keeps e^{-eta h} of its noise per step, not the DDIM
+        paper's linear eta; multistep_table). eta = 0 is the deterministic sampler."""
         from . import parallel
-        lmbd = _check_solver(solver, lmbd, self, grid=grid, t_end=t_end)
+        lmbd = _check_solver(solver, lmbd, self, grid=grid, t_end=t_end, eta=eta)
         # (sample_sharded's launch is guarded: the device status word was read after it, so an asynchronous kernel
         # failure has raised already rather than coming back as silent NaNs)
         kw = {"lmbd": lmbd} if lmbd != 0.0 else {}
@@ -295,20 +335,23 @@ class BaseClassDiffusionModel:
             kw["solver"] = solver
         if solver in _lib.TABLE_SOLVERS:
             kw.update(grid=grid, t_end=t_end)
+            if float(eta) != 0.0:
+                kw["eta"] = float(eta)
         x = parallel.sample_sharded(self, y, num_samples, num_steps, mean, std, precision=precision, **kw)
         return x.cpu().numpy()
 
     def sample_trajectory(self, y, num_samples=2000, num_steps=200, snapshot_every=10, mean=0, std=1, seed=None,
                           chain_offset=0, precision=None, corrector_steps=0, snr=0.16, lmbd=0.0, solver="euler",
-                          grid="logsnr", t_end=None):
+                          grid="logsnr", t_end=None, eta=0.0):
         """The fused sampler with trajectory snapshots (dmip_em_sample_snapshots): returns device tensors
         (x (n_y, num_samples, xdim), snaps (num_steps // snapshot_every, n_y, num_samples, xdim)), snaps[k]
         = the chains after step (k + 1) * snapshot_every of the loop of models/diffusion.py:27-46 (the
         reference returns only the final state). Same chains, RNG and sharding as sample_device; `lmbd` as
         forward (dmip_em_sample_lmbd with snapshots); `solver="heun"`: the states after each full Heun step
         (dmip_ode_sample); `solver="dpm2m"` / `"ddim"` with `grid` and `t_end` as forward: the states after each of
-        their steps (dmip_multistep_sample)."""
-        lmbd = _check_solver(solver, lmbd, self, grid=grid, t_end=t_end)
+        their steps (dmip_multistep_sample; with `eta` != 0 dmip_multistep_sde_sample, the noise included)."""
+        lmbd = _check_solver(solver, lmbd, self, grid=grid, t_end=t_end, eta=eta)
+        eta = float(eta)
         nets, mode = _nets_and_mode(self, NotImplementedError(f"{type(self).__name__}: no fused trajectory sampler"),
                                     cdiffe=True)
         if corrector_steps and mode != _lib.DMIP_SAMPLER_CDIFFE:
@@ -319,7 +362,7 @@ class BaseClassDiffusionModel:
         if prior is not None and (prior.width, prior.n_hidden) != (net.width, net.n_hidden):
             raise ValueError("prior and likelihood networks must have the same hidden layers")
         prec = _fused_precision(precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim,
-                                [h.act for h in handles], solver)
+                                [h.act for h in handles], solver, eta)
         if prec is None:
             raise ValueError("no fused sampler for this network shape / activation")
         snaps = torch.empty(int(num_steps) // int(snapshot_every), ys.shape[0], int(num_samples), self.xdim,
@@ -328,9 +371,10 @@ class BaseClassDiffusionModel:
         if solver in _lib.TABLE_SOLVERS:
             if not 1 <= int(snapshot_every) <= int(num_steps):
                 raise ValueError("snapshot_every must be in [1, num_steps]")
-            table = self._multistep_table(solver, grid, num_steps, t_end, dev)
-            _lib.multistep_sample(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed,
-                                  out, None, snapshot_every, snaps, prec)
+            table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta)
+            launch = _lib.multistep_sde_sample if eta != 0.0 else _lib.multistep_sample
+            launch(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed, out, None,
+                   snapshot_every, snaps, prec)
             return out, snaps
         if solver == "heun":
             if not 1 <= int(snapshot_every) <= int(num_steps):
@@ -517,10 +561,10 @@ class BaseClassDiffusionModel:
                                                              std, seed, out, logq, x0, precision))
         return out, logq
 
-    def _multistep_table(self, solver, grid, num_steps, t_end, dev):
+    def _multistep_table(self, solver, grid, num_steps, t_end, dev, eta=0.0):
         """multistep_table of this model's VP-SDE as the kernels read it: rounded once to f32, on `dev`."""
         base = self.sde.base_sde
-        tab = multistep_table(solver, grid, num_steps, base.beta_min, base.beta_max, self.sde.T, t_end)
+        tab = multistep_table(solver, grid, num_steps, base.beta_min, base.beta_max, self.sde.T, t_end, eta)
         return torch.from_numpy(tab).to(torch.float32).to(dev).contiguous()
 
     def _exec_device(self, y):
@@ -539,7 +583,8 @@ class BaseClassDiffusionModel:
         return ys.reshape(-1, self.ydim).contiguous()
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None):
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None,
+                      eta=0.0):
         """Device-resident samples (n_y, num_samples, xdim) for ys (n_y, ydim) -- no host copy.
         `chain_offset` selects a shard of a larger run; `noise` injects standard normals
         (num_steps + 1, n_y, num_samples, xdim) (slot 0 -> x0) in place of the internal RNG;
@@ -552,7 +597,10 @@ class BaseClassDiffusionModel:
         encode / decode pair.
         `solver="dpm2m"` / `"ddim"` (CDE and Posterior): the few-step samplers of that ODE from a step table
         (dmip_multistep_sample; multistep_table), num_steps network evaluations on `grid` ("logsnr", ending at `t_end`,
-        or "uniform"); x0, seed, chain_offset and precision as for "heun"."""
+        or "uniform"); x0, seed, chain_offset and precision as for "heun". `eta` != 0 (forward): their stochastic
+        variants (dmip_multistep_sde_sample), whose chain draws the Euler sampler's normals, x0 and every step's, from
+        the same stream (the x0 draw is consumed when x0= is given, so the step noise is the same either way); noise=
+        is refused."""
         raise NotImplementedError
 
     def _prepare(self, y, num_samples, num_steps, nets):
@@ -616,15 +664,17 @@ class CDE(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None):
-        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end)
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None,
+                      eta=0.0):
+        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end, eta)
+        eta = float(eta)
         net = self.sde.a
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [net])
         handle = net.dmip_handle(dev, self.xdim)
         seed = _draw_seed() if seed is None else seed
         x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
         prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_CDE, handle.width, handle.n_hidden,
-                                self.xdim, self.ydim, [handle.act], solver)
+                                self.xdim, self.ydim, [handle.act], solver, eta)
         if noise is not None:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
             if tuple(noise.shape) != (int(num_steps) + 1, ys.shape[0], int(num_samples), self.xdim):
@@ -639,13 +689,13 @@ class CDE(BaseClassDiffusionModel):
 
             if solver in _lib.TABLE_SOLVERS:
                 return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0,
-                                              self._multistep_table(solver, grid, num_steps, t_end, dev),
-                                              lambda x, y, tvec, g: self.sde.a(x, y, tvec))
+                                              self._multistep_table(solver, grid, num_steps, t_end, dev, eta),
+                                              lambda x, y, tvec, g: self.sde.a(x, y, tvec), stochastic=eta != 0.0)
             return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
                                    drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
-        table = self._multistep_table(solver, grid, num_steps, t_end, dev) if solver in _lib.TABLE_SOLVERS else None
+        table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta) if solver in _lib.TABLE_SOLVERS else None
         return _fused_launch(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps, mean,
-                             std, seed, out, prec, lmbd, solver, x0, noise, table)
+                             std, seed, out, prec, lmbd, solver, x0, noise, table, eta)
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         from .training import DeviceTrainStep, _plain_adam, device_step_enabled, device_step_ok, fused_config, \
@@ -727,23 +777,28 @@ def _em_device_loop(model, ys, num_samples, num_steps, mean, std, seed, chain_of
     return torch.stack(outs)
 
 
-def _multistep_device_loop(model, ys, num_samples, seed, chain_offset, mean, std, x0, table, score):
+def _multistep_device_loop(model, ys, num_samples, seed, chain_offset, mean, std, x0, table, score, stochastic=False):
     """solver="dpm2m" / "ddim" for shapes without a compiled fused sampler: the update of csrc/dmip_device.h
     MultistepStep from the same f32 table (num_steps, 8) on the device, in its rounding order (f32 tensor ops, no
     fusion), one network launch (dmip_mlp_forward) per network and step. score(x, y, tvec, g) is a (CDE) or
-    g (likelihood + prior) (Posterior). The start states are _em_device_loop's: the loop's own chain-keyed x0, or x0."""
+    g (likelihood + prior) (Posterior). The start states are _em_device_loop's: the loop's own chain-keyed x0, or x0.
+    stochastic (eta != 0): the table's column 7 times the step's normals is added last; the normals are
+    _em_device_loop's, stream sid + 1 + i of the chain-keyed generator, so shards stay bit-identical to the whole."""
     dev = ys.device
     rows = table.cpu()
     outs = []
     with torch.no_grad():
         for k in range(ys.shape[0]):
+            sid = _LOOP_STREAM + (k << 40)
             x = x0[k] if x0 is not None else \
-                _loop_normals(seed, int(chain_offset), _LOOP_STREAM + (k << 40), num_samples, model.xdim, dev) * std + mean
+                _loop_normals(seed, int(chain_offset), sid, num_samples, model.xdim, dev) * std + mean
             d_prev = torch.zeros_like(x)
-            for tau, p, q, cx, c0, c1, g, _ in rows.tolist():
+            for i, (tau, p, q, cx, c0, c1, g, cn) in enumerate(rows.tolist()):
                 a = score(x, ys[k], torch.full((num_samples, 1), tau, device=dev), g)
                 d = p * x + q * a
                 x = (cx * x + c0 * d) + c1 * d_prev
+                if stochastic:
+                    x = x + cn * _loop_normals(seed, int(chain_offset), sid + 1 + i, num_samples, model.xdim, dev)
                 d_prev = d
             outs.append(x)
     return torch.stack(outs)
@@ -843,8 +898,10 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         self.loss_fn = PosteriorLoss
 
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None):
-        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end)
+                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None,
+                      eta=0.0):
+        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end, eta)
+        eta = float(eta)
         if noise is not None:
             raise ValueError("noise injection is only implemented for the fused CDE sampler")
         score = self.sde.a
@@ -856,15 +913,16 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
         if (prior.width, prior.n_hidden) == (lik.width, lik.n_hidden):
             prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width, lik.n_hidden,
-                                    self.xdim, self.ydim, [prior.act, lik.act], solver)
-        table = self._multistep_table(solver, grid, num_steps, t_end, dev) if solver in _lib.TABLE_SOLVERS else None
+                                    self.xdim, self.ydim, [prior.act, lik.act], solver, eta)
+        table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta) if solver in _lib.TABLE_SOLVERS else None
         if prec is not None:
             return _fused_launch(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset,
-                                 num_steps, mean, std, seed, out, prec, lmbd, solver, x0, table=table)
+                                 num_steps, mean, std, seed, out, prec, lmbd, solver, x0, table=table, eta=eta)
         if table is not None:  # a = g (likelihood + prior) at the table's g, as the fused kernel forms it
             return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0, table,
                                           lambda x, y, tvec, g: g * (score.likelihood_net(x, y, tvec) +
-                                                                     score.prior_net(x, tvec)))
+                                                                     score.prior_net(x, tvec)),
+                                          stochastic=eta != 0.0)
         base = self.sde.base_sde
 
         def drift(x, y, tvec):

@@ -61,7 +61,8 @@ def sample_sharded(model, y, num_samples, num_steps, mean, std, seed=None, **sam
     `sampler_kwargs` go to model.sample_device (e.g. CDiffE's corrector_steps / snr, or lmbd= / solver="heun": the
     Heun chains start from the same chain-keyed x0, so their shards are bit-identical to one launch too; likewise
     solver="dpm2m" / "ddim" with their grid= and t_end=, whose step table depends on num_steps and the SDE alone, so
-    every rank builds the same one)."""
+    every rank builds the same one; their eta= is forwarded the same way: the stochastic variants' noise is keyed by
+    the global chain index as the Euler sampler's, so the union stays bit-identical)."""
     from .estimators import _draw_seed
     rank, ws = world()
     dev = model._exec_device(y)

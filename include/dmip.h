@@ -224,7 +224,7 @@ int dmip_ode_sample_supported(int mode, int width, int n_hidden, int xdim, int y
  *   x_{i+1} = (sigma_{i+1} / sigma_i) x_i - alpha_{i+1} expm1(-h_i) D_i,     x_S = d_{S-1}
  *   D_i     = d_i (DDIM; 2M at i = 0), or (1 + 1/(2r)) d_i - (1/(2r)) d_{i-1} with r = h_{i-1} / h_i (2M)
  * The kernels know the table, not the scheme that built it: row i of table_dev [num_steps][DMIP_MULTISTEP_COLS] is
- *   tau_i | p_i q_i | cx_i c0_i c1_i | g_i | 0
+ *   tau_i | p_i q_i | cx_i c0_i c1_i | g_i | cn_i (ignored here: dmip_multistep_sde_sample's noise coefficient)
  * and a step is a = net(x, y, tau_i) (a = g_i (likelihood + prior) for DMIP_SAMPLER_POSTERIOR), then, every operation
  * rounded to f32 and none fused,
  *   d = p_i x + q_i a;   x <- (cx_i x + c0_i d) + c1_i d_prev;   d_prev <- d         (d_prev = 0 before step 0)
@@ -245,6 +245,30 @@ int dmip_multistep_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, 
                           int table_cols, float mean, float stdv, uint64_t seed, int precision, const float* x0_dev,
                           int snapshot_every, float* snap_out_dev, float* x_out_dev, void* stream);
 int dmip_multistep_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision);
+
+/* The stochastic few-step samplers from the same table: SDE-DPM-Solver++(2M) (Lu et al.), ancestral sampling / eta-DDIM
+ * and what lies between (k-diffusion's dpmpp_2m_sde convention). For eta >= 0, in the notation above and for i < S - 1,
+ *   x_{i+1} = (sigma_{i+1} / sigma_i) e^{-eta h_i} x_i + alpha_{i+1} (1 - e^{-(1 + eta) h_i}) D_i
+ *             + sigma_{i+1} sqrt(1 - e^{-2 eta h_i}) xi_i,                               x_S = d_{S-1}
+ * with D_i as above and xi_i standard normal. The kernels again know the table alone; its column 7, which
+ * dmip_multistep_sample ignores, is the noise coefficient here: row i is
+ *   tau_i | p_i q_i | cx_i c0_i c1_i | g_i | cn_i
+ * and a step is the one above with the noise added last, every operation rounded to f32 and none fused:
+ *   d = p_i x + q_i a;   x <- ((cx_i x + c0_i d) + c1_i d_prev) + cn_i xi;   d_prev <- d
+ * Draw order: the chain's stream is the Euler sampler's (dmip_em_sample: seed, chain_offset + chain, y index). Its first
+ * D normals are x0 = stdv n + mean; they are drawn and discarded when x0_dev is given, so the step noise does not depend
+ * on whether x0 was injected. D normals follow each step's network evaluation, on every step including the last (where
+ * a table of the scheme has cn = 0). So a chain's x0 and xi_i are the Euler sampler's, draw for draw. A table with a
+ * zero column 7 gives dmip_multistep_sample's output. A tile handed from one wave to the next carries the generator and
+ * d_prev, so shards of a run are bit-identical to the whole run.
+ * Arguments, their validation order, precisions and shapes: those of dmip_multistep_sample
+ * (dmip_multistep_sde_supported answers for these kernels). */
+int dmip_multistep_sde_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const float* y_dev, int n_y,
+                              int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps,
+                              const float* table_dev, int table_cols, float mean, float stdv, uint64_t seed,
+                              int precision, const float* x0_dev, int snapshot_every, float* snap_out_dev,
+                              float* x_out_dev, void* stream);
+int dmip_multistep_sde_supported(int mode, int width, int n_hidden, int xdim, int ydim, int precision);
 
 /* Samples of the probability-flow ODE together with their model log-density, exact f32, one launch: the steps of
  * dmip_ode_sample's DMIP_SOLVER_HEUN at DMIP_PREC_F32 (same grid, same m, same f32 rounding order, same x0: x_out is
