@@ -8,14 +8,14 @@ F32OBJS := $(CSRC)/dmip_f32.o $(CSRC)/dmip_f32_cde.o $(CSRC)/dmip_f32_post.o $(C
            $(CSRC)/dmip_f32_cde_heun.o $(CSRC)/dmip_f32_post_heun.o $(CSRC)/dmip_flow_sample.o \
            $(CSRC)/dmip_dps_linear.o $(CSRC)/dmip_f32_cde_ms.o $(CSRC)/dmip_f32_post_ms.o \
            $(CSRC)/dmip_f32_cde_ms_sde.o $(CSRC)/dmip_f32_post_ms_sde.o \
-           $(CSRC)/dmip_flow_pairs.o $(CSRC)/dmip_flow_sample_pairs.o
+           $(CSRC)/dmip_flow_pairs.o $(CSRC)/dmip_flow_sample_pairs.o $(CSRC)/dmip_dps_tweedie.o
 X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)/dmip_x3_cdiffe.o $(CSRC)/dmip_x3k.o \
           $(CSRC)/dmip_dps_x3.o $(CSRC)/dmip_x3_cde_heun.o $(CSRC)/dmip_x3_post_heun.o \
           $(CSRC)/dmip_x3_flow.o $(CSRC)/dmip_x3_flow_cde.o $(CSRC)/dmip_x3_flow_post.o \
           $(CSRC)/dmip_x3_flow_sample_cde.o $(CSRC)/dmip_x3_flow_sample_post.o $(CSRC)/dmip_x3_dps_linear.o \
           $(CSRC)/dmip_x3_cde_ms.o $(CSRC)/dmip_x3_post_ms.o $(CSRC)/dmip_x3_cde_ms_sde.o $(CSRC)/dmip_x3_post_ms_sde.o \
           $(CSRC)/dmip_x3_flow_pairs.o $(CSRC)/dmip_x3_flow_pairs_cde.o $(CSRC)/dmip_x3_flow_pairs_post.o \
-          $(CSRC)/dmip_x3_flow_sample_pairs_cde.o $(CSRC)/dmip_x3_flow_sample_pairs_post.o
+          $(CSRC)/dmip_x3_flow_sample_pairs_cde.o $(CSRC)/dmip_x3_flow_sample_pairs_post.o $(CSRC)/dmip_x3_dps_tweedie.o
 # the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, training entry points) and
 # the weight packers (pure host code, dmip_pack.h)
 CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train dmip_capi_dps_linear dmip_pack
@@ -67,6 +67,10 @@ $(CSRC)/dmip_flow_sample.o: $(CSRC)/dmip_flow_sample.hip $(CSRC)/dmip_flow.h $(C
 $(CSRC)/dmip_dps_linear.o: $(CSRC)/dmip_dps_linear.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# the same sampler with the Tweedie-covariance guidance (dps_linear_rows over DpsTweedieChains), exact f32
+$(CSRC)/dmip_dps_tweedie.o: $(CSRC)/dmip_dps_tweedie.hip $(CSRC)/dmip_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_f32.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # the paired flow kernels (one observation per row), exact f32: dmip_flow.h's network with a per-row layer-1 bias
 PAIRSHDRS := $(CSRC)/dmip_pairs.h $(CSRC)/dmip_flow_rows.h $(HDRS)
 $(CSRC)/dmip_flow_pairs.o $(CSRC)/dmip_flow_sample_pairs.o: $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/dmip_flow_pairs.h $(CSRC)/dmip_flow.h $(CSRC)/dmip_f32.h $(PAIRSHDRS)
@@ -99,6 +103,10 @@ $(patsubst %,$(CSRC)/%.o,$(X3PAIRS)): $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/dmip_x3
 
 # the same on the fp32x3 engine (listed before nothing else matches it: an explicit rule beats dmip_x3_%.o)
 $(CSRC)/dmip_x3_dps_linear.o: $(CSRC)/dmip_x3_dps_linear.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# the Tweedie-covariance guidance on the fp32x3 engine (explicit, as dmip_x3_dps_linear.o)
+$(CSRC)/dmip_x3_dps_tweedie.o: $(CSRC)/dmip_x3_dps_tweedie.hip $(CSRC)/dmip_x3_flow.h $(CSRC)/dmip_flow_rows.h $(CSRC)/dmip_x3.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 
 # the k-major multi-tile fp32x3 CDE engine (width 256): its own header

@@ -46,6 +46,7 @@ EXPORTED = (
     "dmip_flow_sample_supported_precision", "dmip_mala_sample", "dmip_dps_linear_supported", "dmip_dps_linear_sample",
     "dmip_multistep_sample", "dmip_multistep_supported", "dmip_flow_pairs_supported", "dmip_flow_logp_pairs",
     "dmip_flow_sample_pairs", "dmip_multistep_sde_sample", "dmip_multistep_sde_supported",
+    "dmip_dps_tweedie_supported", "dmip_dps_tweedie_sample",
 )
 DMIP_SOLVER_EULER, DMIP_SOLVER_HEUN = 0, 1
 SOLVERS = {"euler": DMIP_SOLVER_EULER, "heun": DMIP_SOLVER_HEUN}
@@ -220,6 +221,11 @@ def _declare(lib):
         lib.dmip_multistep_sde_sample.argtypes = [_i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _i64, _i64,
                                                   _i32, _c_void_p, _i32, _f32, _f32, _u64t, _i32, _c_void_p, _i32,
                                                   _c_void_p, _c_void_p, _c_void_p]
+    if hasattr(lib, "dmip_dps_tweedie_sample"):  # additive within ABI 9
+        lib.dmip_dps_tweedie_supported.argtypes = [_i32] * 5
+        lib.dmip_dps_tweedie_sample.argtypes = [_c_void_p, ctypes.POINTER(DmipVpsde), _c_void_p, _c_void_p, _c_void_p,
+                                                _c_void_p, _i32, _i32, _i64, _i64, _i32, _f32, _f32, _u64t, _f32, _i32,
+                                                _c_void_p, _c_void_p]
     for name in EXPORTED:  # every entry point returns int but dmip_last_error
         if name != "dmip_last_error" and hasattr(lib, name):
             getattr(lib, name).restype = _i32
@@ -737,6 +743,22 @@ def dps_linear_sample(prior, sde, A, B, yres, n_chains, chain_offset, num_steps,
                                        int(yres.shape[1]), int(yres.shape[0]), int(n_chains), int(chain_offset),
                                        int(num_steps), float(mean), float(std), _u64(seed), int(step_rule),
                                        float(zeta), precision_code(precision), ptr(out), stream_of(yres.device)))
+
+
+def dps_tweedie_supported(width, n_hidden, xdim, ydim, precision="fp32x3"):
+    return bool(lib().dmip_dps_tweedie_supported(width, n_hidden, xdim, ydim, precision_code(precision)))
+
+
+def dps_tweedie_sample(prior, sde, A, B, H, yres, n_chains, chain_offset, num_steps, mean, std, seed, zeta, out,
+                       precision="fp32x3"):
+    """dmip_dps_tweedie_sample: dps_linear_sample with the Tweedie-covariance guidance. A (ydim, xdim), B (ydim, xdim)
+    = Sigma^-1 A, H (xdim, xdim) = A^T Sigma^-1 A, yres (n_y, ydim) = y - b: contiguous f32 device tensors."""
+    calls["dps_tweedie_sample"] += 1
+    _status_pending.add(_dev_index(yres.device))
+    check(lib().dmip_dps_tweedie_sample(prior.h, ctypes.byref(sde), ptr(A), ptr(B), ptr(H), ptr(yres),
+                                        int(yres.shape[1]), int(yres.shape[0]), int(n_chains), int(chain_offset),
+                                        int(num_steps), float(mean), float(std), _u64(seed), float(zeta),
+                                        precision_code(precision), ptr(out), stream_of(yres.device)))
 
 
 def posterior_loss_grad(prior_layers, lik_layers, surrogate, noise, lam, sde, x, y, t, eps, grad_prior, grad_lik,

@@ -10,6 +10,8 @@
 // every expression below is its result. One kernel does not go through sample_rows: f32_flow_sample_kernel keeps the
 // same text written out, because its spilling W 512 instantiations measured slower through it (dmip_flow_sample.hip).
 #pragma once
+#include <type_traits>
+
 #include "dmip_device.h"
 #include "dmip_internal.h"
 
@@ -244,9 +246,47 @@ __device__ __forceinline__ float vp_var(float t, float bmin, float bdiff) {
 // Sums run over the measurement index first to last, each product rounded (nothing is contracted). A, B_i and y' are
 // wave-uniform: plain loads the compiler may issue as scalar ones. Every lane of a row holds its state and does the
 // same arithmetic; the only stores are the final x. `nonfinite` is ORed with "a kept row's final state is not finite".
-template <int D, int NW, typename Score>
-__device__ __forceinline__ void dps_linear_rows(const DpsLinearChains& p, Rows<NW>& rows, int yi, bool& nonfinite,
+//
+// Chains = DpsTweedieChains (a compile-time rule: the DpsLinearChains instantiations hold none of it) puts the
+// conditional covariance of Tweedie's second-order formula, Cov[x0 | x_tau] = C = (v / alpha^2) K, K = I + v J, into the
+// likelihood of y' given x_tau. With w = B^T r, B = Sigma^-1 A (n_B = 1), and H = A^T Sigma^-1 A (p.H, [D][D]) the push-
+// through identity A^T (Sigma + A C A^T)^-1 = (I + H C)^-1 A^T Sigma^-1 leaves one D x D system per row and step:
+//   K[k][n]  = [k == n] + v J[k][n]              cs = v / (alpha alpha)
+//   Mx[k][n] = [k == n] + sum_r H[k][r] (cs K[r][n])      (r first to last)
+//   u        = adj(Mx) w / det(Mx)               (tweedie_solve: cofactors, no pivoting, no guard on det)
+// and G, lam (the beta rule) and the update are the ones above with this u. J enters as computed, not symmetrised.
+__device__ __forceinline__ void tweedie_solve(const float (&m)[2][2], const float (&w)[2], float (&u)[2]) {
+  const float det = m[0][0] * m[1][1] - m[0][1] * m[1][0];
+  u[0] = (m[1][1] * w[0] - m[0][1] * w[1]) / det;
+  u[1] = (m[0][0] * w[1] - m[1][0] * w[0]) / det;
+}
+// cof[i][j] = m[i+1][j+1] m[i+2][j+2] - m[i+1][j+2] m[i+2][j+1] (indices mod 3: the signed cofactor), det along row 0,
+// u_k = (cof[0][k] w_0 + cof[1][k] w_1 + cof[2][k] w_2) / det
+__device__ __forceinline__ void tweedie_solve(const float (&m)[3][3], const float (&w)[3], float (&u)[3]) {
+  float cof[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+      cof[i][j] = m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
+    }
+  }
+  const float det = m[0][0] * cof[0][0] + m[0][1] * cof[0][1] + m[0][2] * cof[0][2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) u[k] = (cof[0][k] * w[0] + cof[1][k] * w[1] + cof[2][k] * w[2]) / det;
+}
+
+__device__ __forceinline__ const DpsLinearChains& dps_lin(const DpsLinearChains& p) { return p; }
+__device__ __forceinline__ const DpsLinearChains& dps_lin(const DpsTweedieChains& p) { return p.lin; }
+
+template <int D, int NW, typename Chains, typename Score>
+__device__ __forceinline__ void dps_linear_rows(const Chains& pc, Rows<NW>& rows, int yi, bool& nonfinite,
                                                 Score&& score) {
+  constexpr bool kTweedie = std::is_same<Chains, DpsTweedieChains>::value;
+  static_assert(!kTweedie || D == 2 || D == 3, "the closed-form solve is written for D = 2 and D = 3");
+  const DpsLinearChains& p = dps_lin(pc);
   const int S = p.num_steps, M = p.ydim;
   const float* yr = p.yres + (size_t)yi * M;
   for (long long rd = 0; rd < rows.rounds; ++rd) {
@@ -284,6 +324,27 @@ __device__ __forceinline__ void dps_linear_rows(const DpsLinearChains& p, Rows<N
         rr = rr + r * r;
 #pragma unroll
         for (int k = 0; k < D; ++k) u[k] = u[k] + Bi[q * D + k] * r;
+      }
+      if constexpr (kTweedie) {
+        const float cs = var / (mw * mw);
+        float Kc[D][D], Mx[D][D], wv[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          wv[k] = u[k];
+#pragma unroll
+          for (int n = 0; n < D; ++n) Kc[k][n] = cs * ((k == n ? 1.0f : 0.0f) + var * J[k][n]);
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+#pragma unroll
+          for (int n = 0; n < D; ++n) {
+            float a = k == n ? 1.0f : 0.0f;
+#pragma unroll
+            for (int r = 0; r < D; ++r) a = a + pc.H[k * D + r] * Kc[r][n];
+            Mx[k][n] = a;
+          }
+        }
+        tweedie_solve(Mx, wv, u);
       }
       const float lam = p.step_rule == 0 ? p.zeta * p.delta * c.beta : p.zeta / sqrtf(fmaxf(rr, 1e-30f));
       float xi[D];

@@ -504,6 +504,27 @@ struct X3DpsLinearParams {
 bool dps_linear_supported(int width, int n_hidden, int xdim, int ydim);
 hipError_t launch_f32_dps_linear(const F32DpsLinearParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 hipError_t launch_x3_dps_linear(const X3DpsLinearParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+// The same sampler with the Tweedie-covariance guidance (include/dmip.h dmip_dps_tweedie_sample; dmip_dps_tweedie.hip,
+// dmip_x3_dps_tweedie.hip): the chains of dps_linear (B = Sigma^-1 A, n_B = 1, the beta step rule) and H = A^T Sigma^-1
+// A. Their own structs: the dps_linear kernels' arguments stay where they are.
+struct DpsTweedieChains {
+  DpsLinearChains lin;
+  const float* H;             // [D][D]
+};
+struct F32DpsTweedieParams {
+  F32Net net;
+  int n_hidden;
+  DpsTweedieChains chains;
+};
+struct X3DpsTweedieParams {
+  X3Net net;
+  int n_hidden;
+  DpsTweedieChains chains;
+  unsigned int* err;          // device status word (kErrRange)
+};
+// the shapes of dps_linear_supported, on both engines
+hipError_t launch_f32_dps_tweedie(const F32DpsTweedieParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
+hipError_t launch_x3_dps_tweedie(const X3DpsTweedieParams& p, int width, int xdim, int n_y, hipStream_t st, bool* ok);
 // geometry of the x3 images (dmip_x3.h Shape) for the host packer
 int x3_chunk_bytes(int width);
 int x3_tiles_per_chunk(int width);

@@ -1049,7 +1049,7 @@ class DPS(_PriorDiffusionModel):
         return out
 
 
-_LINEAR_GUIDANCES = ('pigdm', 'nll', 'norm')
+_LINEAR_GUIDANCES = ('pigdm', 'nll', 'norm', 'tweedie')
 
 
 def _spd_matrix(Sigma, M):
@@ -1084,14 +1084,22 @@ def linear_guidance_table(A, Sigma, guidance, num_steps, beta_min, beta_max, T):
         return 2.0 * A[None], _lib.DMIP_DPS_STEP_NORM
     if guidance == 'nll':
         return np.linalg.solve(Sigma, A)[None], _lib.DMIP_DPS_STEP_BETA
-    if guidance != 'pigdm':
-        raise ValueError(f"guidance must be one of {_LINEAR_GUIDANCES}")
+    if guidance != 'pigdm':  # ('tweedie' has no per-step table: linear_tweedie_table)
+        raise ValueError("guidance must be one of ('pigdm', 'nll', 'norm')")
     S = int(num_steps)
     Tf = torch.tensor(float(T), dtype=torch.float32)
     tau = (Tf - torch.linspace(0, 1, S + 1, dtype=torch.float32) * Tf)[:S].double().numpy()  # the kernels' step_coef
     v = -np.expm1(-0.5 * tau * tau * (float(beta_max) - float(beta_min)) - tau * float(beta_min))
     AAt = A @ A.T
     return np.stack([np.linalg.solve(Sigma + vi * AAt, A) for vi in v]), _lib.DMIP_DPS_STEP_BETA
+
+
+def linear_tweedie_table(A, Sigma):
+    """The matrices of dmip_dps_tweedie_sample in float64: (B [M][D], H [D][D]) = (Sigma^-1 A, A^T Sigma^-1 A). They
+    depend on neither the number of steps nor the SDE."""
+    A = np.asarray(A, np.float64)
+    B = np.linalg.solve(np.asarray(Sigma, np.float64), A)
+    return B, A.T @ B
 
 
 class LinearDPS(_PriorDiffusionModel):
@@ -1103,6 +1111,13 @@ class LinearDPS(_PriorDiffusionModel):
                                   covariance of x0 given x_tau kept; exact for a Gaussian prior
       guidance='nll'              B = Sigma^-1 A: the DPS likelihood, which drops that term
       guidance='norm'             B = 2 A with the step zeta / ||r|| (Chung et al. Alg. 1)
+      guidance='tweedie'          'pigdm' with the covariance of x0 given x_tau from Tweedie's second-order formula,
+                                  C = (var / mean_weight^2)(I + var J), where 'pigdm' puts var I (right only for a
+                                  prior that is N(0, I) in the network's coordinates): u solves (I + A^T Sigma^-1 A C) u
+                                  = A^T Sigma^-1 r, one D x D system per chain and step, and G = -(I + var J^T) u /
+                                  mean_weight. Exact for a Gaussian prior of any mean and covariance, and stable at
+                                  zeta = 1 on an untrained prior, where 'pigdm' overflows. Its kernel
+                                  is dmip_dps_tweedie_sample
     Fused kernel: dmip_dps_linear_sample (include/dmip.h), one launch for all steps, for every network shape of the
     flow kernels (widths 64 to 512, 1 to 3 hidden layers, xdim 2 or 3) and ydim up to 32; there is no per-step path.
 
@@ -1132,6 +1147,7 @@ class LinearDPS(_PriorDiffusionModel):
         self.guidance = guidance
         self._init_prior(hidden_layers)
         self._table = None       # (key, A, B, b, step rule): device tensors of the last (num_steps, SDE, guidance, device)
+                                 # ('tweedie': (key, A, B, H, b) of the last device)
         self.table_uploads = 0   # instrumentation: how often the table went to a device
 
     @classmethod
@@ -1159,9 +1175,22 @@ class LinearDPS(_PriorDiffusionModel):
             self.table_uploads += 1
         return self._table[1:]
 
+    def tweedie_table(self, dev):
+        """(A, B, H, b) of guidance='tweedie' on `dev`: A, B = Sigma^-1 A (ydim, xdim) and H = A^T Sigma^-1 A (xdim,
+        xdim) as f32 (built in float64, rounded once), b as float64. No entry depends on num_steps or the SDE: cached
+        per device."""
+        key = ('tweedie', str(dev))
+        if self._table is None or self._table[0] != key:
+            B, H = linear_tweedie_table(self.A, self.Sigma)
+            up = lambda v, dt: torch.from_numpy(np.ascontiguousarray(v)).to(dt).to(dev).contiguous()
+            self._table = (key, up(self.A, torch.float32), up(B, torch.float32), up(H, torch.float32),
+                           up(self.b, torch.float64))
+            self.table_uploads += 1
+        return self._table[1:]
+
     def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0, noise=None,
                       precision=None, lmbd=0.0, solver="euler", x0=None):
-        """dmip_dps_linear_sample at `precision` (default self.precision): "fp32x3" (also what "fp16" runs: there is
+        """dmip_dps_linear_sample (guidance='tweedie': dmip_dps_tweedie_sample) at `precision` (default self.precision): "fp32x3" (also what "fp16" runs: there is
         no 16-bit kernel) or "fp32" (exact f32). At the default precision a chain outside fp16's range resamples in
         exact f32 (parallel.sample_checked). A shape without a kernel raises ValueError."""
         _check_solver(solver, lmbd, self, x0)
@@ -1175,14 +1204,22 @@ class LinearDPS(_PriorDiffusionModel):
         pn = self.prior_net
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [pn])
         layers = pn.hidden_layers
+        tweedie = self.guidance == 'tweedie'
+        supported = _lib.dps_tweedie_supported if tweedie else _lib.dps_linear_supported
         if len(set(layers)) != 1 or pn.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST or \
-                not _lib.dps_linear_supported(layers[0], len(layers), self.xdim, self.ydim, prec):
+                not supported(layers[0], len(layers), self.xdim, self.ydim, prec):
             raise ValueError(f"LinearDPS: no compiled kernel for hidden layers {layers}, xdim {self.xdim}, ydim "
                              f"{self.ydim} (equal widths 64 / 128 / 256 / 512, 1 to 3 layers, xdim 2 or 3, nn.Tanh)")
         prior = pn.dmip_handle(dev, self.xdim)
+        seed = _draw_seed() if seed is None else seed
+        if tweedie:
+            A, B, H, b = self.tweedie_table(dev)
+            yres = (ys.double() - b).float().contiguous()
+            _lib.dps_tweedie_sample(prior, sde, A, B, H, yres, num_samples, chain_offset, num_steps, mean, std, seed,
+                                    self.zeta, out, precision=prec)
+            return out
         A, B, b, rule = self.guidance_table(num_steps, dev)
         yres = (ys.double() - b).float().contiguous()
-        seed = _draw_seed() if seed is None else seed
         _lib.dps_linear_sample(prior, sde, A, B, yres, num_samples, chain_offset, num_steps, mean, std, seed, rule,
                                self.zeta, out, precision=prec)
         return out

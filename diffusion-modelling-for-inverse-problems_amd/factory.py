@@ -4,7 +4,7 @@ Extension (not in the reference): config['model'] == 'DPS' builds the guided sam
 (estimators.DPS) on `forward_model`, with optional config keys 'zeta' (default 0.005) and 'guidance'
 ('norm' | 'nll', default 'norm'); its training loss is the prior DSM (DSMLoss). config['model'] == 'LinearDPS' builds
 estimators.LinearDPS for the linear problem: `forward_model` is the problem object (LinearForwardProblem: its A, b and
-Sigma), the keys are 'zeta' (default 1.0) and 'guidance' ('pigdm' | 'nll' | 'norm', default 'pigdm'), the loss DSMLoss."""
+Sigma), the keys are 'zeta' (default 1.0) and 'guidance' ('pigdm' | 'nll' | 'norm' | 'tweedie', default 'pigdm'), the loss DSMLoss."""
 from .estimators import CDE, DPS, CDiffE, LinearDPS, PosteriorDiffusionEstimator
 from .losses import DSM_PDELoss, DSMLoss, PINNLoss, PINNLoss2
 

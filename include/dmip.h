@@ -600,6 +600,29 @@ int dmip_dps_linear_sample(const dmip_mlp* prior, const dmip_vpsde* sde, const f
                            int num_steps, float mean, float stdv, uint64_t seed, int step_rule, float zeta,
                            int precision, float* x_out_dev, void* stream);
 
+/* dmip_dps_linear_sample with the Tweedie-covariance guidance (ABI 9, additive; "Tweedie moment projection", Boys et
+ * al. 2023): the likelihood of y given x_tau with Cov[x0 | x_tau] taken from Tweedie's second-order formula,
+ * C = (v / alpha^2)(I + v J), where the table of 'pigdm' hard-codes v I (exact only for a prior that is N(0, I)). With a
+ * Gaussian prior of any mean and covariance the rule is exact, and x0_hat + C^T u is E[x0 | x_tau, y]. Per chain and
+ * step i, in the notation above:
+ *   s, J   = prior(x, tau_i) and ds/dx
+ *   x0_hat = (x + v_i s) / alpha_i;  r = y' - A x0_hat;  w = B^T r            B = Sigma^-1 A, one matrix
+ *   K      = I + v_i J;  C = (v_i / alpha_i^2) K                               J as computed, not symmetrised
+ *   solve (I + H C) u = w                                                       H = A^T Sigma^-1 A
+ *   G      = -(K^T u) / alpha_i = -(u + v_i J^T u) / alpha_i
+ *   x     <- x + delta (g_i^2 s + beta_i x / 2) + sqrt(delta) g_i xi  -  zeta delta beta_i G
+ * The D x D system is the push-through form of A^T (Sigma + A C A^T)^-1: no M x M matrix is formed and C need not be
+ * positive definite. It is solved in f32 by the adjugate over the determinant, with no guard: a zero or non-finite
+ * determinant makes the final state non-finite, which dmip_device_status reports (fp32x3) as for dmip_dps_linear_sample.
+ *   B_dev [M][D];  H_dev [D][D] (both built in float64 and rounded once by the caller);  every other argument, the
+ *   shapes, precisions, RNG, sharding, validation order and status classes are dmip_dps_linear_sample's (a null
+ *   pointer, H_dev included, is DMIP_ERR_INVALID). dmip_dps_tweedie_supported answers as dmip_dps_linear_supported. */
+int dmip_dps_tweedie_supported(int width, int n_hidden, int xdim, int ydim, int precision);
+int dmip_dps_tweedie_sample(const dmip_mlp* prior, const dmip_vpsde* sde, const float* A_dev, const float* B_dev,
+                            const float* H_dev, const float* yres_dev, int ydim, int n_y, int64_t n_chains,
+                            int64_t chain_offset, int num_steps, float mean, float stdv, uint64_t seed, float zeta,
+                            int precision, float* x_out_dev, void* stream);
+
 /* ---- PosteriorLoss training step ------------------------------------------ */
 /* Loss value, components and the parameter gradients of PosteriorLoss(forward_model, a, b, lam)(sde, x,
  * y, t) + loss.backward() (losses.py:293-386) as PosteriorDiffusionEstimator.train_epoch drives it
