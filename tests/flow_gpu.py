@@ -1,8 +1,10 @@
 """What the GPU tests of the flow kernels share (test_gpu_flow_logp.py, test_gpu_flow_sample.py, test_gpu_flow_x3.py):
-the accuracy gate, the fixture and seeded models, and the device-side helpers. A plain module beside flow_ref.py."""
+the accuracy gate (flow_cases.py's), the fixture and seeded models, and the device-side helpers. A plain module beside
+flow_ref.py."""
 import numpy as np
 import torch
 
+import flow_cases as FC
 import flow_sample_ref as FS
 import oracle as O
 from conftest import state_from_npz
@@ -18,17 +20,11 @@ def dev(a):
     return torch.from_numpy(np.array(a)).to(DEV)  # (a copy: the shared references are read-only)
 
 
-def gate(name, got, ref64, ref32, k=4, scaled=True, tag=""):
-    """e_gpu <= k e_cpu + 1e-6 max(1, max |f64|) (`scaled`; else + 1e-6), e_gpu = max |gpu - f64| and e_cpu = max |f32
-    restatement - f64| over the same rows. k = 4 is every flow test's: each module's docstring derives it."""
-    got, ref64, ref32 = (np.asarray(v, np.float64) for v in (got, ref64, ref32))
-    e_gpu = np.abs(got - ref64).max()
-    e_cpu = np.abs(ref32 - ref64).max()
-    tol = k * e_cpu + 1e-6 * (max(1.0, np.abs(ref64).max()) if scaled else 1.0)
-    print(f"{tag}{name}: e_gpu = {e_gpu:.3e}, e_cpu = {e_cpu:.3e}, e_gpu / e_cpu = {e_gpu / max(e_cpu, 1e-300):.2f}, "
-          f"max |ref| = {np.abs(ref64).max():.4g}, tol = {tol:.3e}")
-    assert np.all(np.isfinite(got))
-    assert e_gpu <= tol, (name, e_gpu, e_cpu, tol)
+def gate(name, got, ref64, ref32, scaled=True, tag=""):
+    """flow_cases.gate, every flow test's: e_gpu <= K max(e_cpu, 1e-7), K = 8 (flow_cases.CASE_K by `name`), with
+    e_gpu = max |gpu - f64| and e_cpu = max |f32 restatement - f64| over the same rows, and never above the gate it
+    replaced, 4 e_cpu + 1e-6 max(1, max |f64|) (`scaled`; else + 1e-6). flow_cases.py derives K."""
+    FC.gate(name, got, ref64, ref32, scaled=scaled, tag=tag)
 
 
 def load_linear(net, params):
@@ -65,6 +61,15 @@ def post(dmip, golden):
     m.sde.a.prior_net.load_state_dict(state_from_npz(golden("ckpt_prior_scat.npz")))
     m.sde.a.likelihood_net.load_state_dict(state_from_npz(golden("posterior_loss.npz"), "lik_"))
     return m
+
+
+def case_model(dmip, golden, cid):
+    """The model of a flow_cases case (its paired form shares the network)."""
+    name = FC.PAIRED.get(cid, cid)
+    if name in FC.SHAPES:
+        W, NL, xd, yd, _, seed = FC.SHAPES[name]
+        return seeded(dmip, W, NL, xd, yd, seed)[0]
+    return {"a": lin, "b": scat, "d": post}[name](dmip, golden)
 
 
 def sample_reference(params, x0, y, S, prior=None):

@@ -2,12 +2,12 @@
 reference's own evaluation (tests/golden/flow_logp.npz) and the f64 restatement (tests/flow_ref.py). Needs an
 MI355X: `pytest -m gpu`.
 
-Gate of every accuracy test: with e_gpu = max |logp_gpu - logp_f64| and e_cpu = max |logp_f32_cpu - logp_f64| (the
-same scheme evaluated in f32 on the CPU: the reference's own f32 arithmetic for the fixture cases, flow_ref's f32
-run for the shapes without a fixture), e_gpu <= 4 e_cpu + 1e-6; the factor 4 covers the different summation order
-of the MFMA chain and the different tanh. The latent x_S gets the same gate. For the seeded shapes there is one f64
-and one f32 run of flow_ref per network, shared and sliced by the ragged cases; e_gpu and e_cpu are taken over the
-same rows.
+Gate of every accuracy test (flow_gpu.gate; tests/flow_cases.py derives it): with e_gpu = max |logp_gpu - logp_f64| and
+e_cpu = max |logp_f32_cpu - logp_f64| (the same scheme evaluated in f32 on the CPU: the reference's own f32 arithmetic
+for the fixture cases, flow_ref's f32 run for the shapes without a fixture), e_gpu <= 8 max(e_cpu, 1e-7) and never
+above the gate it replaced, 4 e_cpu + 1e-6 (the smaller of the two wherever e_cpu > 2.5e-7). The latent x_S gets the
+same gate. For the seeded shapes there is one f64 and one f32 run of flow_ref per network, shared and sliced by the
+ragged cases; e_gpu and e_cpu are taken over the same rows.
 """
 import numpy as np
 import pytest
@@ -27,7 +27,7 @@ def _need_gpu():
 
 
 def _gate(name, got, ref64, ref32):
-    gate(name, got, ref64, ref32, scaled=False)  # |logp| and |x_S| are O(1) here: the additive term is 1e-6
+    gate(name, got, ref64, ref32, scaled=False, tag="F32GATE ")  # (the replaced gate's additive term: 1e-6)
 
 
 def _fixture_model(dmip, golden, case):
@@ -93,11 +93,8 @@ def test_ragged_rows_vs_flow_ref(dmip, name, n):
     logp, lat = m.log_prob(torch.from_numpy(x[:n]).to(DEV), torch.from_numpy(ys[0]).to(DEV), num_steps=S,
                            return_latent=True)
     assert tuple(logp.shape) == (n,) and tuple(lat.shape) == (n, x.shape[1])
-    e_cpu = np.abs(l32[:n] - l64[:n]).max()
-    e_gpu = np.abs(logp.cpu().numpy() - l64[:n]).max()
-    print(f"{name} n={n}: e_gpu = {e_gpu:.3e}, e_cpu = {e_cpu:.3e}, ratio {e_gpu / e_cpu:.2f}")
-    assert np.all(np.isfinite(logp.cpu().numpy())) and e_gpu <= 4 * e_cpu + 1e-6, (e_gpu, e_cpu)
-    assert np.abs(lat.cpu().numpy() - z64[:n]).max() <= 4 * np.abs(z32[:n] - z64[:n]).max() + 1e-6
+    _gate(f"{name} n={n} logp", logp.cpu().numpy(), l64[:n], l32[:n])
+    _gate(f"{name} n={n} latent", lat.cpu().numpy(), z64[:n], z32[:n])
 
 
 def test_multi_y(dmip):
@@ -109,7 +106,7 @@ def test_multi_y(dmip):
     assert logp.shape == (3, n)
     for i, lo in enumerate((0, 7, 20)):
         l64, _, l32, _ = ref[i]
-        assert np.abs(logp[i] - l64[lo:lo + n]).max() <= 4 * np.abs(l32[lo:lo + n] - l64[lo:lo + n]).max() + 1e-6
+        _gate(f"multi-y {i} logp", logp[i], l64[lo:lo + n], l32[lo:lo + n])
     assert np.abs(logp[0] - ref[1][0][:n]).max() > 1e-3  # the ys do differ
 
 

@@ -3,13 +3,13 @@
 tests/flow_sample_ref.py), the fp32x3 Heun sampler, themselves (shards, single rows, seed path / x0 path), the
 exact-f32 kernels and evaluate.importance_posterior. Needs an MI355X: `pytest -m gpu`.
 
-Gate of every accuracy test (the exact-f32 flow tests' form): with e_gpu = max |gpu - f64| and e_cpu = max |f32
+Gate of every accuracy test (flow_cases.gate, every flow test's): with e_gpu = max |gpu - f64| and e_cpu = max |f32
 restatement - f64| over the same rows -- the restatement's own f32 run, never the code under test --
-    e_gpu <= K e_cpu + 1e-6 max(1, max |f64|)
-with K = 4, the exact-f32 kernels' factor (measured e_gpu / e_cpu on the device: DESIGN.md 3g; 0.3 to 3.03 over
-all 55 gates but one, 3.61 on the single-row log_prob case whose e_cpu is one row's 1.8e-7 -- the factor 10 the Heun
-tests allow the split engine was not needed). One f64 and one f32 run of a restatement per network and y, shared
-read-only by the cases that slice them.
+    e_gpu <= K max(e_cpu, 1e-7),   K = 8
+and never above the gate it replaced, 4 e_cpu + 1e-6 max(1, max |f64|). tests/flow_cases.py derives K and
+tests/test_flow_accuracy_host.py proves on the CPU that a tangent path with a lost product or flushed lo halves misses
+it; measured e_gpu / max(e_cpu, 1e-7) on the device: DESIGN.md 3g. One f64 and one f32 run of a restatement per
+network and y, shared read-only by the cases that slice them.
 """
 import functools
 import importlib
@@ -18,16 +18,16 @@ import numpy as np
 import pytest
 import torch
 
+import flow_cases as FC
 import flow_ref as FR
 import flow_sample_ref as FS
 import heun_ref as HR
-from flow_gpu import DEV, gate, seeded
+from flow_gpu import DEV, case_model, gate, seeded
 from flow_gpu import bits as _bits, dev as _dev, device_x0 as _device_x0, sample_reference as _sample_reference
 from flow_gpu import lin as _lin, post as _post, scat as _scat
 
 pytestmark = pytest.mark.gpu
 
-K = 4
 X3 = "fp32x3"
 
 
@@ -43,7 +43,7 @@ def ev(dmip):
 
 
 def _gate(name, got, ref64, ref32):
-    gate(name, got, ref64, ref32, k=K, tag="X3GATE ")
+    gate(name, got, ref64, ref32, tag="X3GATE ")
 
 
 # ------------------------------------------------------------------------------------- 1. fixture checkpoints
@@ -95,13 +95,8 @@ def test_sample_fixture_cases(dmip, golden, case):
 
 
 # ------------------------------------------------------------------------------------- 1. seeded networks
-SHAPES = {  # name: (W, n_hidden, xdim, ydim, rows of the shared reference, weight seed); S = 4
-    "w64": (64, 3, 2, 2, 37, 301),
-    "w128": (128, 3, 2, 2, 19, 302),
-    "w64x1": (64, 1, 3, 5, 21, 305),
-    "w512": (512, 3, 3, 23, 21, 304),
-}
-S_SEEDED = 4
+SHAPES = FC.SHAPES  # name: (W, n_hidden, xdim, ydim, rows of the shared reference, weight seed); S = 4
+S_SEEDED = FC.S_SEEDED
 _refs = {}
 
 
@@ -161,6 +156,35 @@ def test_multi_y(dmip):
         _gate(f"multi-y {i} logq", logq[i].cpu().numpy(), q64[:n], q32[:n])
         _gate(f"multi-y {i} x", xs[i].cpu().numpy(), x64[:n], x32[:n])
     assert np.abs(logp[0].cpu().numpy() - ref[1]["logp"][0][:n]).max() > 1e-3  # the ys do differ
+
+
+# ------------------------------------------------------------------------------------- 1. the cases of flow_cases
+@pytest.mark.parametrize("scheme", FC.SCHEMES)
+@pytest.mark.parametrize("prec", [X3, "fp32"])
+@pytest.mark.parametrize("cid", [c for c in FC.CASES if c not in FC.PAIRED])
+def test_flow_cases_through_the_gate(dmip, golden, cid, prec, scheme):
+    """Every case that tests/test_flow_accuracy_host.py proves the gate sharp on, on both engines and both entry
+    points, x0 injected: one launch each (case d: its two ys in one), against flow_cases' own restatements."""
+    m = case_model(dmip, golden, cid)
+    d = FC.data(cid)
+    r64, r32 = FC.refs(cid, scheme)
+    one = len(d.runs) == 1
+    pick = (lambda a: _dev(a[0])) if one else _dev
+    ys = pick(np.stack([r.y for r in d.runs]))
+    call = "flow_logp" if scheme == "logp" else "flow_sample"
+    before = dmip._lib.calls.get(call, 0)
+    if scheme == "logp":
+        logp, lat = m.log_prob(pick(np.stack([r.x for r in d.runs])), ys, num_steps=d.S, return_latent=True,
+                               precision=prec)
+        out = {"logp": logp, "latent": lat}
+    else:
+        x, logq = m.sample_with_log_prob(ys, len(d.runs[0].x0), d.S, x0=pick(np.stack([r.x0 for r in d.runs])),
+                                         precision=prec)
+        out = {"logq": logq, "x": x}
+    assert dmip._lib.calls[call] == before + 1
+    for arr in FC.ARRAYS[scheme]:
+        got = out[arr].cpu().numpy().reshape(r64[arr].shape)
+        gate(f"case {cid} {prec} {arr}", got, r64[arr], r32[arr], tag="FLOWGATE ")
 
 
 # ------------------------------------------------------------------------------------- 2. the fp32x3 Heun sampler

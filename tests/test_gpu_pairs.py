@@ -4,10 +4,11 @@ restatements with a per-row y (tests/flow_ref.py, tests/flow_sample_ref.py: scor
 (n, ydim) y is taken row by row), against the per-y entry points and against themselves (single rows, slabs, shards),
 and evaluate.hpd_coverage. Needs an MI355X: `pytest -m gpu`.
 
-Gate of every accuracy test: flow_gpu.gate at k = 4, e_gpu <= 4 e_cpu + 1e-6 (scaled by max(1, max |f64|) for the
-sampler's x and logq, as in test_gpu_flow_sample.py), with e_cpu from the f32 restatement over the same rows. One f64
-and one f32 run of each restatement per network, shared read-only by the cases that slice them; rows are independent
-in the restatement too, so the first n rows of the reference are the reference of the first n pairs.
+Gate of every accuracy test: flow_gpu.gate (tests/flow_cases.py), e_gpu <= 8 max(e_cpu, 1e-7) and never above the gate
+it replaced, 4 e_cpu + 1e-6 (scaled by max(1, max |f64|) for the sampler's x and logq, as in test_gpu_flow_sample.py),
+with e_cpu from the f32 restatement over the same rows. One f64 and one f32 run of each restatement per network, shared
+read-only by the cases that slice them; rows are independent in the restatement too, so the first n rows of the
+reference are the reference of the first n pairs.
 """
 import importlib
 
@@ -15,10 +16,11 @@ import numpy as np
 import pytest
 import torch
 
+import flow_cases as FC
 import flow_ref as FR
 import flow_sample_ref as FS
 import heun_ref as HR
-from flow_gpu import DEV, bits, dev, device_x0, gate, lin, post, seeded
+from flow_gpu import DEV, bits, case_model, dev, device_x0, gate, lin, post, seeded
 from test_gpu_flow_logp import SHAPES
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +117,29 @@ def test_log_prob_pairs_vs_restatement(dmip, golden, name, prec):
     gate(f"{name} {prec} latent", lat.cpu().numpy(), z64, z32, scaled=False)
     only = m.log_prob_pairs(dev(x), dev(ys), num_steps=S, precision=prec)
     np.testing.assert_array_equal(bits(only), bits(logp))
+
+
+@pytest.mark.parametrize("scheme", FC.SCHEMES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("cid", list(FC.PAIRED))
+def test_flow_cases_pairs_through_the_gate(dmip, golden, cid, prec, scheme):
+    """The paired cases that tests/test_flow_accuracy_host.py proves the gate sharp on (a different y in every row; the
+    seeded shapes and the fixture Posterior pair), both engines, both entry points, x0 injected: one launch each."""
+    m = case_model(dmip, golden, cid)
+    d = FC.data(cid)
+    (run,) = d.runs
+    r64, r32 = FC.refs(cid, scheme)
+    call = "flow_logp_pairs" if scheme == "logp" else "flow_sample_pairs"
+    before = dmip._lib.calls.get(call, 0)
+    if scheme == "logp":
+        logp, lat = m.log_prob_pairs(dev(run.x), dev(run.y), num_steps=d.S, return_latent=True, precision=prec)
+        out = {"logp": logp, "latent": lat}
+    else:
+        x, logq = m.sample_with_log_prob_pairs(dev(run.y), d.S, x0=dev(run.x0), precision=prec)
+        out = {"logq": logq, "x": x}
+    assert dmip._lib.calls[call] == before + 1
+    for arr in FC.ARRAYS[scheme]:
+        gate(f"case {cid} {prec} {arr}", out[arr].cpu().numpy(), r64[arr], r32[arr], tag="FLOWGATE ")
 
 
 # ------------------------------------------------------------------------------------- 2. ragged rows

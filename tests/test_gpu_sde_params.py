@@ -253,8 +253,8 @@ def test_unfused_loop(dmip, tag, solver):
 @pytest.mark.parametrize("cid", list(C.FLOW))
 @pytest.mark.parametrize("tag", TAGS)
 def test_log_prob_vs_flow_ref(dmip, tag, cid, prec):
-    """log_prob and its latent against flow_ref.log_prob: the flow tests' gate e_gpu <= 4 e_cpu + 1e-6 (scaled by
-    max(1, |f64|) on the split engine, as tests/test_gpu_flow_x3.py). Two observations equal their single launches."""
+    """log_prob and its latent against flow_ref.log_prob: the flow tests' gate e_gpu <= 8 max(e_cpu, 1e-7), never above
+    the 4 e_cpu + 1e-6 it replaced (that one scaled by max(1, |f64|) on the split engine; tests/flow_cases.py). Two observations equal their single launches."""
     m, params, prior, x, y = C.flow_model(dmip, cid)
     _at(dmip, m, tag)
     sde = C.SDES[tag]
