@@ -16,9 +16,9 @@ X3OBJS := $(CSRC)/dmip_x3.o $(CSRC)/dmip_x3_cde.o $(CSRC)/dmip_x3_post.o $(CSRC)
           $(CSRC)/dmip_x3_cde_ms.o $(CSRC)/dmip_x3_post_ms.o $(CSRC)/dmip_x3_cde_ms_sde.o $(CSRC)/dmip_x3_post_ms_sde.o \
           $(CSRC)/dmip_x3_flow_pairs.o $(CSRC)/dmip_x3_flow_pairs_cde.o $(CSRC)/dmip_x3_flow_pairs_post.o \
           $(CSRC)/dmip_x3_flow_sample_pairs_cde.o $(CSRC)/dmip_x3_flow_sample_pairs_post.o $(CSRC)/dmip_x3_dps_tweedie.o
-# the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, training entry points) and
-# the weight packers (pure host code, dmip_pack.h)
-CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_train dmip_capi_dps_linear dmip_pack
+# the host sources: the C-ABI layer by concern (handles and upload, sampling entry points, the probability-flow entry
+# points, training entry points, linear guided sampling) and the weight packers (pure host code, dmip_pack.h)
+CAPI := dmip_capi_pack dmip_capi_sample dmip_capi_flow dmip_capi_train dmip_capi_dps_linear dmip_pack
 CAPIOBJS := $(patsubst %,$(CSRC)/%.o,$(CAPI))
 OBJS := $(CSRC)/dmip_kernels.o $(CSRC)/dmip_train.o $(CSRC)/dmip_eval.o $(CSRC)/dmip_surrogate.o $(CSRC)/dmip_gemm.o $(CSRC)/dmip_jets.o $(CSRC)/dmip_step.o $(F32OBJS) $(X3OBJS) $(CAPIOBJS)
 HDRS := $(CSRC)/dmip_device.h $(CSRC)/dmip_internal.h include/dmip.h

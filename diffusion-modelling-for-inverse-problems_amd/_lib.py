@@ -448,22 +448,30 @@ def multistep_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, pr
     return bool(lib().dmip_multistep_supported(mode, width, n_hidden, xdim, ydim, precision_code(precision)))
 
 
+def _multistep(name, mode, net, prior, y, n_chains, chain_offset, num_steps, table, mean, std, seed, out, x0,
+               snapshot_every, snaps, precision):
+    """The body of multistep_sample and multistep_sde_sample: `name` is the wrapper's (its `calls` key, the name in its
+    message and, behind dmip_, its entry point)."""
+    if tuple(table.shape) != (int(num_steps), DMIP_MULTISTEP_COLS) or table.dtype != torch.float32 or \
+            not table.is_contiguous() or table.device != y.device:
+        raise ValueError(f"{name}: table must be a contiguous f32 (num_steps, DMIP_MULTISTEP_COLS) tensor on y's "
+                         "device")
+    calls[name] += 1
+    _status_pending.add(_dev_index(y.device))
+    n_y, ydim = y.shape
+    check(getattr(lib(), "dmip_" + name)(int(mode), net.h, _h(prior), ptr(y), n_y, ydim, net.xdim, int(n_chains),
+                                         int(chain_offset), int(num_steps), ptr(table), int(table.shape[1]),
+                                         float(mean), float(std), _u64(seed), precision_code(precision), ptr(x0),
+                                         int(snapshot_every), ptr(snaps), ptr(out), stream_of(y.device)))
+
+
 def multistep_sample(mode, net, prior, y, n_chains, chain_offset, num_steps, table, mean, std, seed, out, x0=None,
                      snapshot_every=0, snaps=None, precision="fp32x3"):
     """dmip_multistep_sample: the fused CDE / Posterior few-step sampler of the probability-flow ODE (DPM-Solver++(2M),
     DDIM) from `table`, a contiguous f32 device tensor (num_steps, DMIP_MULTISTEP_COLS) (estimators.multistep_table);
     x0 (n_y, n_chains, xdim) replaces the chain's own start state."""
-    if tuple(table.shape) != (int(num_steps), DMIP_MULTISTEP_COLS) or table.dtype != torch.float32 or \
-            not table.is_contiguous() or table.device != y.device:
-        raise ValueError("multistep_sample: table must be a contiguous f32 (num_steps, DMIP_MULTISTEP_COLS) tensor on "
-                         "y's device")
-    calls["multistep_sample"] += 1
-    _status_pending.add(_dev_index(y.device))
-    n_y, ydim = y.shape
-    check(lib().dmip_multistep_sample(int(mode), net.h, _h(prior), ptr(y), n_y, ydim, net.xdim, int(n_chains),
-                                      int(chain_offset), int(num_steps), ptr(table), int(table.shape[1]), float(mean),
-                                      float(std), _u64(seed), precision_code(precision), ptr(x0), int(snapshot_every),
-                                      ptr(snaps), ptr(out), stream_of(y.device)))
+    _multistep("multistep_sample", mode, net, prior, y, n_chains, chain_offset, num_steps, table, mean, std, seed, out,
+               x0, snapshot_every, snaps, precision)
 
 
 def multistep_sde_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32x3"):
@@ -476,17 +484,8 @@ def multistep_sde_sample(mode, net, prior, y, n_chains, chain_offset, num_steps,
     from `table` as multistep_sample, whose column 7 is the noise coefficient (estimators.multistep_table(eta=)). A
     chain draws the Euler sampler's normals: x0's first (consumed also when `x0` replaces the start state), then one
     set after each step's network evaluation."""
-    if tuple(table.shape) != (int(num_steps), DMIP_MULTISTEP_COLS) or table.dtype != torch.float32 or \
-            not table.is_contiguous() or table.device != y.device:
-        raise ValueError("multistep_sde_sample: table must be a contiguous f32 (num_steps, DMIP_MULTISTEP_COLS) tensor "
-                         "on y's device")
-    calls["multistep_sde_sample"] += 1
-    _status_pending.add(_dev_index(y.device))
-    n_y, ydim = y.shape
-    check(lib().dmip_multistep_sde_sample(int(mode), net.h, _h(prior), ptr(y), n_y, ydim, net.xdim, int(n_chains),
-                                          int(chain_offset), int(num_steps), ptr(table), int(table.shape[1]),
-                                          float(mean), float(std), _u64(seed), precision_code(precision), ptr(x0),
-                                          int(snapshot_every), ptr(snaps), ptr(out), stream_of(y.device)))
+    _multistep("multistep_sde_sample", mode, net, prior, y, n_chains, chain_offset, num_steps, table, mean, std, seed,
+               out, x0, snapshot_every, snaps, precision)
 
 
 def flow_logp_supported(width, n_hidden, xdim, ydim=0, mode=DMIP_SAMPLER_CDE, precision="fp32"):

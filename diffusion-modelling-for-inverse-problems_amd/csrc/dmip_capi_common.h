@@ -1,6 +1,7 @@
-// Shared by the C-ABI sources (dmip_capi_pack.cpp, dmip_capi_sample.cpp, dmip_capi_train.cpp): error reporting, the
-// handle structs behind include/dmip.h's opaque types, and the small helpers more than one of them uses. Host code
-// only; no kernel includes this header.
+// Shared by the C-ABI sources (dmip_capi_pack.cpp, dmip_capi_sample.cpp, dmip_capi_flow.cpp, dmip_capi_dps_linear.cpp,
+// dmip_capi_train.cpp): error reporting, the handle structs behind include/dmip.h's opaque types, and the helpers more
+// than one of them uses (the schedule, the networks' check, the per-y layer-1 preps, the fp32x3 range refusal, the
+// device status word). Host code only; no kernel includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -126,6 +127,14 @@ struct StreamScratch {
 };
 
 inline dmip::F32Net f32_net(const dmip_mlp* n) { return dmip::F32Net{n->f32_l1, n->f32_stream, n->f32_bias}; }
+// the fp32x3 images over (x, t) (a CDiffE launch swaps in the full layer-1 image: em_sample_x3)
+inline dmip::X3Net x3_net(const dmip_mlp* n) { return dmip::X3Net{n->x3_l1, n->x3_stream, n->x3_bias}; }
+
+// the device status word of the stream's device into a kernel's `err` field
+inline int status_word_or_fail(unsigned*& err, hipStream_t st) {
+  err = status_word(dmip::stream_device(st));
+  return err ? DMIP_OK : fail(DMIP_ERR_ALLOC, "device status word");
+}
 
 // the activation chain's code in the exact-f32 kernels (dmip_f32.h act_f32): 0 tanh, 1 SiLU. Only the exact-f32
 // forward and the exact-f32 CDE sampler compile the SiLU chain; every other kernel computes tanh.
@@ -135,6 +144,81 @@ inline int act_refused(const char* what) {
   return fail(DMIP_ERR_UNSUPPORTED, std::string(what) +
                                         ": the SiLU chain is compiled for the exact-f32 forward and the exact-f32 "
                                         "CDE sampler only (DMIP_PREC_F32)");
+}
+
+// the VP-SDE schedule of a launch: each value evaluated in double and rounded once to the kernels' f32.
+// `step` is T / num_steps (the samplers' delta, the flow's h); `sqrt_step` where the kernel takes it
+inline void fill_schedule(const dmip_vpsde& sde, int num_steps, float& T, float& bmin, float& bdiff, float& step,
+                          float* sqrt_step = nullptr) {
+  T = (float)sde.T;
+  bmin = (float)sde.beta_min;
+  bdiff = (float)(sde.beta_max - sde.beta_min);
+  step = (float)(sde.T / (double)num_steps);
+  if (sqrt_step) *sqrt_step = (float)std::sqrt(sde.T / (double)num_steps);
+}
+
+// "no compiled <kind> (mode m[, precision p]) for width w, layers l, xdim x[, ydim y]"
+inline int no_kernel(const char* kind, int mode, const dmip_mlp* net, int xdim, int ydim = -1, int precision = -1) {
+  return fail(DMIP_ERR_UNSUPPORTED,
+              std::string("no compiled ") + kind + " (mode " + std::to_string(mode) +
+                  (precision >= 0 ? ", precision " + std::to_string(precision) : "") + ") for width " +
+                  std::to_string(net->width) + ", layers " + std::to_string(net->n_hidden) + ", xdim " +
+                  std::to_string(xdim) + (ydim >= 0 ? ", ydim " + std::to_string(ydim) : ""));
+}
+
+// the networks and sizes of a sampler (`who` "sampler") or flow ("flow_logp", "flow_sample", ...) launch. net0: the
+// CDE / CDiffE network or the Posterior likelihood; net1: the Posterior prior (else null). `rows`: `count` is a
+// log-density call's row count, else the chain count (checked with `offset`)
+inline int check_nets(const char* who, const dmip_mlp* net0, const dmip_mlp* net1, int out_expected, int xdim, int ydim,
+                      int n_y, bool rows, int64_t count, int64_t offset, int num_steps, const dmip_vpsde* sde) {
+  if (net0->layout != DMIP_INPUT_X_Y_T) return fail(DMIP_ERR_INVALID, std::string(who) + " needs an x,y,t network");
+  if (xdim != net0->xdim || net0->out_dim != out_expected)
+    return fail(DMIP_ERR_INVALID, "xdim does not match the network");
+  if (ydim != net0->in_dim - xdim - 1) return fail(DMIP_ERR_INVALID, "ydim does not match the network");
+  if (net1) {
+    if (net1->layout != DMIP_INPUT_X_T || net1->xdim != xdim || net1->out_dim != xdim)
+      return fail(DMIP_ERR_INVALID, "prior must be an x,t network with out_dim == xdim");
+    if (net1->width != net0->width || net1->n_hidden != net0->n_hidden)
+      return fail(DMIP_ERR_UNSUPPORTED, "prior and likelihood networks must have the same hidden layers");
+  }
+  if (n_y < 1 || n_y > 65535) return fail(DMIP_ERR_INVALID, "n_y must be in [1, 65535]");
+  if (rows && count < 0) return fail(DMIP_ERR_INVALID, "negative row count");
+  if (!rows && (count < 0 || offset < 0)) return fail(DMIP_ERR_INVALID, "negative chain count/offset");
+  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
+  if (!(sde->T > 0.0)) return fail(DMIP_ERR_INVALID, "T must be > 0");
+  return DMIP_OK;
+}
+
+// the exact-f32 engine's per-y layer-1 images (the samplers and the flow): y is constant per y index, so layer 1 runs
+// over (x, t) with W1_y y + b1 folded into the bias column
+inline int f32_l1_prep(StreamScratch& l1y, const dmip_mlp* net, const float* y_dev, int n_y, int xdim, int ydim,
+                       hipStream_t st) {
+  const int k1q = (xdim + 2 + 3) / 4;
+  if (int rc = l1y.alloc((size_t)n_y * (net->width / 16) * k1q * 64 * sizeof(float), st)) return rc;
+  dmip::F32L1PrepParams lp{net->w1, net->b1, y_dev, (float*)l1y.ptr, net->width, net->in_dim, xdim, ydim, k1q};
+  const hipError_t e = dmip::launch_f32_l1_prep(lp, n_y, st);
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "f32 layer-1 prep launch");
+}
+
+// the refusal of every fp32x3 entry point whose split images could not be packed (`what`: "|w|" or "scaled |w|")
+inline int x3_range_refused(const std::string& who, const char* what, double range) {
+  return fail(DMIP_ERR_UNSUPPORTED, who + ": a weight is outside the fp16 range of the split engine (largest " + what +
+                                        " " + std::to_string(range) + " > 65504); use DMIP_PREC_F32");
+}
+inline int x3_check_range(const dmip_mlp* net0, const dmip_mlp* net1) {  // the samplers' and the flow's networks
+  for (const dmip_mlp* n : {net0, net1})
+    if (n && n->x3_range > 0.0) return x3_range_refused("fp32x3", "scaled |w|", n->x3_range);
+  return DMIP_OK;
+}
+
+// the fp32x3 engine's per-y layer-1 bias (the samplers and the flow): y is constant per y index, so c (b1 + W1_y y)
+// becomes layer 1's bias (f64 prep)
+inline int x3_bias_prep(StreamScratch& bias_y, const dmip_mlp* net, const float* y_dev, int n_y, int xdim, int ydim,
+                        hipStream_t st) {
+  if (int rc = bias_y.alloc((size_t)n_y * net->width * sizeof(float), st)) return rc;
+  dmip::X3BiasPrepParams bp{net->w1, net->b1, y_dev, (float*)bias_y.ptr, net->width, net->in_dim, xdim, ydim};
+  const hipError_t e = dmip::launch_x3_bias_prep(bp, n_y, st);
+  return e == hipSuccess ? DMIP_OK : hip_fail(e, "x3 bias prep launch");
 }
 
 inline int surrogate_n_wg(int64_t rows, hipStream_t st) {

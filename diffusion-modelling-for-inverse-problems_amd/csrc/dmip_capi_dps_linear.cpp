@@ -29,9 +29,7 @@ int check_dps(const dmip_mlp* prior, const dmip_vpsde* sde, int ydim, int n_y, i
                                           ", layers " + std::to_string(prior->n_hidden) + ", xdim " +
                                           std::to_string(xdim));
   if (x3 && prior->x3_range > 0.0)
-    return fail(DMIP_ERR_UNSUPPORTED,
-                what + " (fp32x3): a weight is outside the fp16 range of the split engine (largest scaled |w| " +
-                    std::to_string(prior->x3_range) + " > 65504); use DMIP_PREC_F32");
+    return x3_range_refused(what + " (fp32x3)", "scaled |w|", prior->x3_range);
   if (x3 ? !prior->x3_stream : (!prior->f32_l1 || prior->f32_k1q != (xdim + 2 + 3) / 4))
     return fail(DMIP_ERR_UNSUPPORTED, what + ": the prior has no image for this precision");
   return DMIP_OK;
@@ -51,11 +49,7 @@ dmip::DpsLinearChains dps_chains(const dmip_vpsde* sde, const float* A_dev, cons
   c.ydim = ydim;
   c.n_B = n_B;
   c.step_rule = step_rule;
-  c.T = (float)sde->T;
-  c.bmin = (float)sde->beta_min;
-  c.bdiff = (float)(sde->beta_max - sde->beta_min);
-  c.delta = (float)(sde->T / (double)num_steps);
-  c.sqrt_delta = (float)std::sqrt(sde->T / (double)num_steps);
+  fill_schedule(*sde, num_steps, c.T, c.bmin, c.bdiff, c.delta, &c.sqrt_delta);
   c.mean = mean;
   c.stdv = stdv;
   c.zeta = zeta;
@@ -94,11 +88,10 @@ int dmip_dps_linear_sample(const dmip_mlp* prior, const dmip_vpsde* sde, const f
   hipError_t e;
   if (x3) {
     dmip::X3DpsLinearParams p{};
-    p.net = dmip::X3Net{prior->x3_l1, prior->x3_stream, prior->x3_bias};
+    p.net = x3_net(prior);
     p.n_hidden = prior->n_hidden;
     p.chains = c;
-    p.err = status_word(dmip::stream_device(st));
-    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+    if (int rc = status_word_or_fail(p.err, st)) return rc;
     e = dmip::launch_x3_dps_linear(p, prior->width, prior->xdim, n_y, st, &ok);
   } else {
     dmip::F32DpsLinearParams p{};
@@ -136,11 +129,10 @@ int dmip_dps_tweedie_sample(const dmip_mlp* prior, const dmip_vpsde* sde, const 
   hipError_t e;
   if (x3) {
     dmip::X3DpsTweedieParams p{};
-    p.net = dmip::X3Net{prior->x3_l1, prior->x3_stream, prior->x3_bias};
+    p.net = x3_net(prior);
     p.n_hidden = prior->n_hidden;
     p.chains = c;
-    p.err = status_word(dmip::stream_device(st));
-    if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+    if (int rc = status_word_or_fail(p.err, st)) return rc;
     e = dmip::launch_x3_dps_tweedie(p, prior->width, prior->xdim, n_y, st, &ok);
   } else {
     dmip::F32DpsTweedieParams p{};

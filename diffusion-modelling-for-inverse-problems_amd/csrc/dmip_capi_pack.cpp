@@ -1,7 +1,7 @@
 // libdmip.so C-ABI (include/dmip.h), handles and library state: dmip_mlp_create and dmip_surrogate_create (validate,
 // pack on the host with dmip_pack.h, upload every image, publish the handle), the network forward, the error text and
-// the device status words. The sampling entry points are in dmip_capi_sample.cpp, the training ones in
-// dmip_capi_train.cpp.
+// the device status words. The sampling entry points are in dmip_capi_sample.cpp, the probability-flow ones in
+// dmip_capi_flow.cpp, linear guided sampling in dmip_capi_dps_linear.cpp, the training ones in dmip_capi_train.cpp.
 #include <initializer_list>
 #include <map>
 #include <memory>

@@ -1,8 +1,7 @@
 // libdmip.so C-ABI, sampling entry points: the fused samplers of the three engines (16-bit, exact f32, fp32x3), the
-// probability-flow log-likelihood, the surrogate's forward / log-posterior, MH and DPS, the RNG and schedule probes,
-// and the *_supported queries. Argument validation first, then stream-ordered launches.
+// surrogate's forward / log-posterior, MH and DPS, the RNG and schedule probes, and the samplers' *_supported queries
+// (the probability-flow entry points: dmip_capi_flow.cpp). Argument validation first, then stream-ordered launches.
 #include "dmip_capi_common.h"
-#include "dmip_pairs.h"
 
 using namespace dmip_capi;
 
@@ -47,17 +46,6 @@ struct SampleArgs {
   bool table_sde = false;           // dmip_multistep_sde_sample: SOLVER_TABLE_SDE (the table's column 7 is read)
 };
 
-// the VP-SDE schedule of a launch: each value evaluated in double and rounded once to the kernels' f32.
-// `step` is T / num_steps (the samplers' delta, the flow's h); `sqrt_step` where the kernel takes it
-void fill_schedule(const dmip_vpsde& sde, int num_steps, float& T, float& bmin, float& bdiff, float& step,
-                   float* sqrt_step = nullptr) {
-  T = (float)sde.T;
-  bmin = (float)sde.beta_min;
-  bdiff = (float)(sde.beta_max - sde.beta_min);
-  step = (float)(sde.T / (double)num_steps);
-  if (sqrt_step) *sqrt_step = (float)std::sqrt(sde.T / (double)num_steps);
-}
-
 // the fields SamplerParams, F32SamplerParams and X3SamplerParams share. c_mu / c_sig are step_coef's lambda factors:
 // the Python scalars (1 - 0.5 lmbd) and (1 - lmbd) ** 0.5, evaluated in double and rounded once to the f32 torch
 // multiplies the tensor g by (exactly 1, 1 at lmbd = 0)
@@ -79,54 +67,10 @@ int fill_common(P& p, const SampleArgs& a, hipStream_t st) {
   p.mean = a.mean;
   p.stdv = a.stdv;
   p.seed = a.seed;
-  p.err = status_word(dmip::stream_device(st));
-  if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+  if (int rc = status_word_or_fail(p.err, st)) return rc;
   p.debug_flags = debug_no_handover();
   p.spin_limit = p.debug_flags ? (1u << 10) : (1u << 22);
   return DMIP_OK;
-}
-
-// "no compiled <kind> (mode m[, precision p]) for width w, layers l, xdim x[, ydim y]"
-int no_kernel(const char* kind, int mode, const dmip_mlp* net, int xdim, int ydim = -1, int precision = -1) {
-  return fail(DMIP_ERR_UNSUPPORTED,
-              std::string("no compiled ") + kind + " (mode " + std::to_string(mode) +
-                  (precision >= 0 ? ", precision " + std::to_string(precision) : "") + ") for width " +
-                  std::to_string(net->width) + ", layers " + std::to_string(net->n_hidden) + ", xdim " +
-                  std::to_string(xdim) + (ydim >= 0 ? ", ydim " + std::to_string(ydim) : ""));
-}
-
-// the networks and sizes of a sampler (`who` "sampler") or log-likelihood ("flow_logp") launch. net0: the CDE /
-// CDiffE network or the Posterior likelihood; net1: the Posterior prior (else null). `rows`: `count` is the flow's
-// row count, else the chain count (checked with `offset`)
-int check_nets(const char* who, const dmip_mlp* net0, const dmip_mlp* net1, int out_expected, int xdim, int ydim,
-               int n_y, bool rows, int64_t count, int64_t offset, int num_steps, const dmip_vpsde* sde) {
-  if (net0->layout != DMIP_INPUT_X_Y_T) return fail(DMIP_ERR_INVALID, std::string(who) + " needs an x,y,t network");
-  if (xdim != net0->xdim || net0->out_dim != out_expected)
-    return fail(DMIP_ERR_INVALID, "xdim does not match the network");
-  if (ydim != net0->in_dim - xdim - 1) return fail(DMIP_ERR_INVALID, "ydim does not match the network");
-  if (net1) {
-    if (net1->layout != DMIP_INPUT_X_T || net1->xdim != xdim || net1->out_dim != xdim)
-      return fail(DMIP_ERR_INVALID, "prior must be an x,t network with out_dim == xdim");
-    if (net1->width != net0->width || net1->n_hidden != net0->n_hidden)
-      return fail(DMIP_ERR_UNSUPPORTED, "prior and likelihood networks must have the same hidden layers");
-  }
-  if (n_y < 1 || n_y > 65535) return fail(DMIP_ERR_INVALID, "n_y must be in [1, 65535]");
-  if (rows && count < 0) return fail(DMIP_ERR_INVALID, "negative row count");
-  if (!rows && (count < 0 || offset < 0)) return fail(DMIP_ERR_INVALID, "negative chain count/offset");
-  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
-  if (!(sde->T > 0.0)) return fail(DMIP_ERR_INVALID, "T must be > 0");
-  return DMIP_OK;
-}
-
-// the exact-f32 engine's per-y layer-1 images (the samplers and the flow): y is constant per y index, so layer 1 runs
-// over (x, t) with W1_y y + b1 folded into the bias column
-int f32_l1_prep(StreamScratch& l1y, const dmip_mlp* net, const float* y_dev, int n_y, int xdim, int ydim,
-                hipStream_t st) {
-  const int k1q = (xdim + 2 + 3) / 4;
-  if (int rc = l1y.alloc((size_t)n_y * (net->width / 16) * k1q * 64 * sizeof(float), st)) return rc;
-  dmip::F32L1PrepParams lp{net->w1, net->b1, y_dev, (float*)l1y.ptr, net->width, net->in_dim, xdim, ydim, k1q};
-  const hipError_t e = dmip::launch_f32_l1_prep(lp, n_y, st);
-  return e == hipSuccess ? DMIP_OK : hip_fail(e, "f32 layer-1 prep launch");
 }
 
 // exact-f32 samplers (dmip_f32.h): same loop, RNG and sharding as the 16-bit kernels; arguments
@@ -173,27 +117,6 @@ bool x3p_enabled() {
 }
 #endif
 
-// the refusal of every fp32x3 entry point whose split images could not be packed (`what`: "|w|" or "scaled |w|")
-int x3_range_refused(const char* who, const char* what, double range) {
-  return fail(DMIP_ERR_UNSUPPORTED, std::string(who) + ": a weight is outside the fp16 range of the split engine " +
-                                        "(largest " + what + " " + std::to_string(range) + " > 65504); use DMIP_PREC_F32");
-}
-int x3_check_range(const dmip_mlp* net0, const dmip_mlp* net1) {  // the samplers' and the flow's networks
-  for (const dmip_mlp* n : {net0, net1})
-    if (n && n->x3_range > 0.0) return x3_range_refused("fp32x3", "scaled |w|", n->x3_range);
-  return DMIP_OK;
-}
-
-// the fp32x3 engine's per-y layer-1 bias (the samplers and the flow): y is constant per y index, so c (b1 + W1_y y)
-// becomes layer 1's bias (f64 prep)
-int x3_bias_prep(StreamScratch& bias_y, const dmip_mlp* net, const float* y_dev, int n_y, int xdim, int ydim,
-                 hipStream_t st) {
-  if (int rc = bias_y.alloc((size_t)n_y * net->width * sizeof(float), st)) return rc;
-  dmip::X3BiasPrepParams bp{net->w1, net->b1, y_dev, (float*)bias_y.ptr, net->width, net->in_dim, xdim, ydim};
-  const hipError_t e = dmip::launch_x3_bias_prep(bp, n_y, st);
-  return e == hipSuccess ? DMIP_OK : hip_fail(e, "x3 bias prep launch");
-}
-
 // fp32-accurate split-fp16 samplers (dmip_x3.h): same loop, RNG and sharding as the other engines;
 // arguments already validated by em_sample_impl
 int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const SampleArgs& a) {
@@ -204,9 +127,10 @@ int em_sample_x3(int mode, const dmip_mlp* net0, const dmip_mlp* net1, const Sam
     return no_kernel("f32x3 sampler", mode, net0, xdim, ydim);
   hipStream_t st = (hipStream_t)a.stream;
   dmip::X3SamplerParams p{};
-  p.net[0] = dmip::X3Net{mode == DMIP_SAMPLER_CDIFFE ? net0->x3_l1_full : net0->x3_l1, net0->x3_stream, net0->x3_bias};
+  p.net[0] = x3_net(net0);
+  if (mode == DMIP_SAMPLER_CDIFFE) p.net[0].l1 = net0->x3_l1_full;  // every input column
   if (mode == DMIP_SAMPLER_CDIFFE && net0->x3_stream_l1r) p.net[0].stream = net0->x3_stream_l1r;  // L1R layout
-  if (net1) p.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
+  if (net1) p.net[1] = x3_net(net1);
   p.n_hidden = net0->n_hidden;
   StreamScratch bias_y;
   // Heun and the table-driven multistep sampler: the one-tile engine only (dmip_x3.h); x3s / x3k keep Euler
@@ -579,364 +503,6 @@ int dmip_em_sample_stamps(const dmip_mlp* net, const dmip_vpsde* sde, const floa
 
 }  // extern "C"
 
-namespace {
-
-// the flow entry points' precision: exact f32 (dmip_flow.hip, dmip_flow_sample.hip), or the fp32x3 engine
-// (dmip_x3_flow.h) -- which DMIP_PREC_FP16 / BF16 run as well: there is no 16-bit flow kernel (as dmip_ode_sample's
-// Heun routing has none)
-int check_flow_precision(int precision) {
-  if (precision != DMIP_PREC_FP16 && precision != DMIP_PREC_F32 && precision != DMIP_PREC_F32X3)
-    return fail(DMIP_ERR_INVALID, "unknown precision");
-  return DMIP_OK;
-}
-
-// what em_sample_x3 checks before an fp32x3 launch: the networks have their split images
-int x3_flow_check(const char* kind, int mode, const dmip_mlp* net, const dmip_mlp* net1, int xdim) {
-  if (int rc = x3_check_range(net, net1)) return rc;
-  if (!net->x3_stream || (net1 && !net1->x3_stream)) return no_kernel(kind, mode, net, xdim, -1, DMIP_PREC_F32X3);
-  return DMIP_OK;
-}
-
-// what a flow launch needs beside its rows or chains: the images' pointers and the engine's per-y layer-1 data
-// (P: X3FlowParams / X3FlowSampleParams, with the device status word; F32FlowParams / F32FlowSampleParams)
-template <typename P>
-int x3_flow_prep(P& p, StreamScratch& bias_y, const dmip_mlp* net, const dmip_mlp* net1, const float* y_dev, int n_y,
-                 int xdim, int ydim, hipStream_t st) {
-  p.net[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
-  if (net1) p.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
-  p.n_hidden = net->n_hidden;
-  if (int rc = x3_bias_prep(bias_y, net, y_dev, n_y, xdim, ydim, st)) return rc;
-  p.bias_y = (float*)bias_y.ptr;
-  p.err = status_word(dmip::stream_device(st));
-  return p.err ? DMIP_OK : fail(DMIP_ERR_ALLOC, "device status word");
-}
-template <typename P>
-int f32_flow_prep(P& p, StreamScratch& l1y, const dmip_mlp* net, const dmip_mlp* net1, const float* y_dev, int n_y,
-                  int xdim, int ydim, hipStream_t st) {
-  p.net[0] = f32_net(net);
-  if (net1) p.net[1] = f32_net(net1);
-  p.n_hidden = net->n_hidden;
-  if (int rc = f32_l1_prep(l1y, net, y_dev, n_y, xdim, ydim, st)) return rc;
-  p.l1y = (float*)l1y.ptr;
-  return DMIP_OK;
-}
-
-// the rows of a log-likelihood launch, whichever engine runs it
-dmip::FlowRows fill_rows(const dmip_vpsde& sde, const float* x_dev, float* logp_out_dev, float* latent_out_dev,
-                         int64_t n, int num_steps) {
-  dmip::FlowRows r{x_dev, logp_out_dev, latent_out_dev, n, num_steps};
-  fill_schedule(sde, num_steps, r.T, r.bmin, r.bdiff, r.h);
-  return r;
-}
-
-// the chains of a flow_sample launch, whichever engine runs it
-dmip::FlowChains fill_chains(const dmip_vpsde& sde, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps,
-                             float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
-                             float* logq_out_dev) {
-  dmip::FlowChains c{x0_dev, x_out_dev, logq_out_dev, n_chains, chain_offset, num_steps};
-  fill_schedule(sde, num_steps, c.T, c.bmin, c.bdiff, c.delta);
-  c.mean = mean;
-  c.stdv = stdv;
-  c.seed = seed;
-  c.base = -0.5 * (double)xdim * 1.8378770664093453 - (double)xdim * std::log((double)stdv);  // log 2 pi
-  return c;
-}
-
-// log p(x | y) along the probability-flow ODE; every argument is validated before any device work
-int flow_logp_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
-                   const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
-                   float* latent_out_dev, int precision, void* stream) {
-  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
-    return fail(DMIP_ERR_INVALID, "flow_logp: CDE and Posterior estimators only");
-  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
-  if (!net || !sde || !x_dev || !y_dev || !logp_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
-    return fail(DMIP_ERR_INVALID, "null argument");
-  if (int rc = check_flow_precision(precision)) return rc;
-  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
-  if (int rc = check_nets("flow_logp", net, net1, xdim, xdim, ydim, n_y, true, n, 0, num_steps, sde)) return rc;
-  if (f32_act(net) || (net1 && f32_act(net1)))
-    return fail(DMIP_ERR_UNSUPPORTED, "flow_logp: the tanh chain only (no SiLU log-likelihood kernel)");
-  const bool x3 = precision != DMIP_PREC_F32;
-  if (!(x3 ? dmip::x3_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)
-           : dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)))
-    return no_kernel("log-likelihood kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = x3 ? x3_flow_check("log-likelihood kernel", mode, net, net1, xdim) : DMIP_OK) return rc;
-  if (n == 0) return DMIP_OK;
-  dmip::X3FlowParams px{};  // the selected engine's is filled and launched
-  dmip::F32FlowParams pf{};
-  px.rows = pf.rows = fill_rows(*sde, x_dev, logp_out_dev, latent_out_dev, n, num_steps);
-  StreamScratch per_y;  // the engine's per-y layer-1 bias or image
-  if (int rc = x3 ? x3_flow_prep(px, per_y, net, net1, y_dev, n_y, xdim, ydim, st)
-                  : f32_flow_prep(pf, per_y, net, net1, y_dev, n_y, xdim, ydim, st))
-    return rc;
-  bool ok = false;
-  const hipError_t e = x3 ? dmip::launch_x3_flow(px, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok)
-                          : dmip::launch_f32_flow(pf, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
-  if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled log-likelihood kernel");
-  return e == hipSuccess ? DMIP_OK : hip_fail(e, "flow_logp launch");
-}
-
-// samples of the probability-flow ODE with their log-density; every argument is validated before any device work
-int flow_sample_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
-                     int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
-                     float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev, float* logq_out_dev,
-                     int precision, void* stream) {
-  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
-    return fail(DMIP_ERR_INVALID, "flow_sample: CDE and Posterior estimators only");
-  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
-  if (n_chains < 1) return fail(DMIP_ERR_INVALID, "n_chains must be >= 1");
-  if (!(stdv > 0.0f)) return fail(DMIP_ERR_INVALID, "stdv must be > 0");
-  if (!net || !sde || !y_dev || !x_out_dev || !logq_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
-    return fail(DMIP_ERR_INVALID, "null argument");
-  if (int rc = check_flow_precision(precision)) return rc;
-  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
-  if (int rc = check_nets("flow_sample", net, net1, xdim, xdim, ydim, n_y, false, n_chains, chain_offset, num_steps,
-                          sde))
-    return rc;
-  if (f32_act(net) || (net1 && f32_act(net1)))
-    return fail(DMIP_ERR_UNSUPPORTED, "flow_sample: the tanh chain only (no SiLU kernel)");
-  const bool x3 = precision != DMIP_PREC_F32;
-  if (!(x3 ? dmip::x3_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)
-           : dmip::f32_flow_sample_supported(mode, net->width, net->n_hidden, xdim, ydim)))
-    return no_kernel("flow_sample kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = x3 ? x3_flow_check("flow_sample kernel", mode, net, net1, xdim) : DMIP_OK) return rc;
-  dmip::X3FlowSampleParams px{};  // the selected engine's is filled and launched
-  dmip::F32FlowSampleParams pf{};
-  px.chains = pf.chains =
-      fill_chains(*sde, xdim, n_chains, chain_offset, num_steps, mean, stdv, seed, x0_dev, x_out_dev, logq_out_dev);
-  StreamScratch per_y;  // the engine's per-y layer-1 bias or image
-  if (int rc = x3 ? x3_flow_prep(px, per_y, net, net1, y_dev, n_y, xdim, ydim, st)
-                  : f32_flow_prep(pf, per_y, net, net1, y_dev, n_y, xdim, ydim, st))
-    return rc;
-  bool ok = false;
-  const hipError_t e = x3 ? dmip::launch_x3_flow_sample(px, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok)
-                          : dmip::launch_f32_flow_sample(pf, mode, net->width, net->n_hidden, xdim, ydim, n_y, st, &ok);
-  if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled flow_sample kernel");
-  return e == hipSuccess ? DMIP_OK : hip_fail(e, "flow_sample launch");
-}
-
-// ---- the paired entry points: one observation per row (dmip_pairs.h)
-// rows per slab: the [rows][W] layer-1 bias scratch stays within 32 MiB (test hook, not ABI: DMIP_PAIRS_SLAB_ROWS=k
-// forces k rows per slab). Rows are independent, so the slabs of a call give the bits of one launch
-int64_t pairs_slab_rows(int width) {
-  if (const char* e = getenv("DMIP_PAIRS_SLAB_ROWS")) {
-    const long long v = atoll(e);
-    if (v >= 1) return (int64_t)v;
-  }
-  return (int64_t)((32u << 20) / ((size_t)width * sizeof(float)));
-}
-// (the kernels index the scratch with 32-bit offsets: a forced slab stays below 2^31 floats)
-int64_t pairs_slab_bound(int64_t slab, int width) { return std::min<int64_t>(slab, ((int64_t)1 << 31) / width - 1); }
-
-// what both paired entry points check after their own arguments: the networks, the activation chain, the shape
-int pairs_check(const char* who, int mode, const dmip_mlp* net, const dmip_mlp* net1, const dmip_vpsde* sde, int ydim,
-                int xdim, int64_t n, int64_t offset, bool rows, int num_steps, bool x3) {
-  if (int rc = check_nets(who, net, net1, xdim, xdim, ydim, 1, rows, n, offset, num_steps, sde)) return rc;
-  if (f32_act(net) || (net1 && f32_act(net1)))
-    return fail(DMIP_ERR_UNSUPPORTED, std::string(who) + ": the tanh chain only (no SiLU kernel)");
-  if (!(x3 ? dmip::x3_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)
-           : dmip::f32_flow_supported(mode, net->width, net->n_hidden, xdim, ydim)))
-    return no_kernel("paired flow kernel", mode, net, xdim, -1, x3 ? DMIP_PREC_F32X3 : -1);
-  return x3 ? x3_flow_check("paired flow kernel", mode, net, net1, xdim) : DMIP_OK;
-}
-
-// a slab's layer-1 biases c_i (and, exact f32, the shared zero-bias layer-1 image) on the stream
-int pairs_prep(StreamScratch& bias, StreamScratch& l1, const dmip_mlp* net, const float* y_dev, int64_t rows, int xdim,
-               int ydim, bool x3, hipStream_t st) {
-  const int k1q = (xdim + 2 + 3) / 4;
-  if (int rc = bias.alloc((size_t)rows * net->width * sizeof(float), st)) return rc;
-  if (!x3)
-    if (int rc = l1.alloc((size_t)(net->width / 16) * k1q * 64 * sizeof(float), st)) return rc;
-  dmip::PairsPrepParams pp{net->w1, net->b1, y_dev, (float*)bias.ptr, (float*)l1.ptr, rows, net->width, net->in_dim,
-                           xdim, ydim, k1q, x3 ? (double)dmip::kPairsTanhScale : 1.0};
-  const hipError_t e = dmip::launch_pairs_prep(pp, st);
-  return e == hipSuccess ? DMIP_OK : hip_fail(e, "paired layer-1 bias prep launch");
-}
-
-int flow_logp_pairs_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
-                         const float* x_dev, const float* y_dev, int ydim, int xdim, int64_t n, int num_steps,
-                         float* logp_out_dev, float* latent_out_dev, int precision, void* stream) {
-  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
-    return fail(DMIP_ERR_INVALID, "flow_logp_pairs: CDE and Posterior estimators only");
-  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
-  if (n < 1) return fail(DMIP_ERR_INVALID, "n must be >= 1");
-  if (!net || !sde || !x_dev || !y_dev || !logp_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
-    return fail(DMIP_ERR_INVALID, "null argument");
-  if (int rc = check_flow_precision(precision)) return rc;
-  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
-  const bool x3 = precision != DMIP_PREC_F32;
-  if (int rc = pairs_check("flow_logp_pairs", mode, net, net1, sde, ydim, xdim, n, 0, true, num_steps, x3)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t slab = pairs_slab_bound(pairs_slab_rows(net->width), net->width);
-  for (int64_t r0 = 0; r0 < n; r0 += slab) {
-    const int64_t rows = std::min<int64_t>(slab, n - r0);
-    StreamScratch bias, l1;
-    if (int rc = pairs_prep(bias, l1, net, y_dev + (size_t)r0 * ydim, rows, xdim, ydim, x3, st)) return rc;
-    const dmip::FlowRows fr = fill_rows(*sde, x_dev + (size_t)r0 * xdim, logp_out_dev + r0,
-                                        latent_out_dev ? latent_out_dev + (size_t)r0 * xdim : nullptr, rows, num_steps);
-    bool ok = false;
-    hipError_t e;
-    if (x3) {
-      dmip::X3FlowPairsParams p{};
-      p.x.net[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
-      if (net1) p.x.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
-      p.x.n_hidden = net->n_hidden;
-      p.x.bias_y = p.row_bias = (const float*)bias.ptr;
-      p.x.rows = fr;
-      p.x.err = status_word(dmip::stream_device(st));
-      if (!p.x.err) return fail(DMIP_ERR_ALLOC, "device status word");
-      e = dmip::launch_x3_flow_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
-    } else {
-      dmip::F32FlowPairsParams p{};
-      p.f.net[0] = f32_net(net);
-      if (net1) p.f.net[1] = f32_net(net1);
-      p.f.n_hidden = net->n_hidden;
-      p.f.l1y = (const float*)l1.ptr;
-      p.row_bias = (const float*)bias.ptr;
-      p.f.rows = fr;
-      e = dmip::launch_f32_flow_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
-    }
-    if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled paired log-likelihood kernel");
-    if (e != hipSuccess) return hip_fail(e, "flow_logp_pairs launch");
-  }
-  return DMIP_OK;
-}
-
-int flow_sample_pairs_impl(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
-                           const float* y_dev, int ydim, int xdim, int64_t n, int64_t chain_offset, int num_steps,
-                           float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
-                           float* logq_out_dev, int precision, void* stream) {
-  if (mode != DMIP_SAMPLER_CDE && mode != DMIP_SAMPLER_POSTERIOR)
-    return fail(DMIP_ERR_INVALID, "flow_sample_pairs: CDE and Posterior estimators only");
-  if (num_steps < 1) return fail(DMIP_ERR_INVALID, "num_steps must be >= 1");
-  if (n < 1) return fail(DMIP_ERR_INVALID, "n must be >= 1");
-  if (!(stdv > 0.0f)) return fail(DMIP_ERR_INVALID, "stdv must be > 0");
-  if (!net || !sde || !y_dev || !x_out_dev || !logq_out_dev || (mode == DMIP_SAMPLER_POSTERIOR && !prior))
-    return fail(DMIP_ERR_INVALID, "null argument");
-  if (int rc = check_flow_precision(precision)) return rc;
-  const dmip_mlp* net1 = mode == DMIP_SAMPLER_POSTERIOR ? prior : nullptr;
-  const bool x3 = precision != DMIP_PREC_F32;
-  if (int rc = pairs_check("flow_sample_pairs", mode, net, net1, sde, ydim, xdim, n, chain_offset, false, num_steps,
-                           x3))
-    return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t slab = pairs_slab_bound(pairs_slab_rows(net->width), net->width);
-  for (int64_t r0 = 0; r0 < n; r0 += slab) {
-    const int64_t rows = std::min<int64_t>(slab, n - r0);
-    StreamScratch bias, l1;
-    if (int rc = pairs_prep(bias, l1, net, y_dev + (size_t)r0 * ydim, rows, xdim, ydim, x3, st)) return rc;
-    const dmip::FlowChains fc =
-        fill_chains(*sde, xdim, rows, chain_offset + r0, num_steps, mean, stdv, seed,
-                    x0_dev ? x0_dev + (size_t)r0 * xdim : nullptr, x_out_dev + (size_t)r0 * xdim, logq_out_dev + r0);
-    bool ok = false;
-    hipError_t e;
-    if (x3) {
-      dmip::X3FlowSamplePairsParams p{};
-      p.x.net[0] = dmip::X3Net{net->x3_l1, net->x3_stream, net->x3_bias};
-      if (net1) p.x.net[1] = dmip::X3Net{net1->x3_l1, net1->x3_stream, net1->x3_bias};
-      p.x.n_hidden = net->n_hidden;
-      p.x.bias_y = p.row_bias = (const float*)bias.ptr;
-      p.x.chains = fc;
-      p.x.err = status_word(dmip::stream_device(st));
-      if (!p.x.err) return fail(DMIP_ERR_ALLOC, "device status word");
-      e = dmip::launch_x3_flow_sample_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
-    } else {
-      dmip::F32FlowSamplePairsParams p{};
-      p.f.net[0] = f32_net(net);
-      if (net1) p.f.net[1] = f32_net(net1);
-      p.f.n_hidden = net->n_hidden;
-      p.f.l1y = (const float*)l1.ptr;
-      p.row_bias = (const float*)bias.ptr;
-      p.f.chains = fc;
-      e = dmip::launch_f32_flow_sample_pairs(p, mode, net->width, net->n_hidden, xdim, ydim, st, &ok);
-    }
-    if (!ok) return fail(DMIP_ERR_UNSUPPORTED, "no compiled paired flow_sample kernel");
-    if (e != hipSuccess) return hip_fail(e, "flow_sample_pairs launch");
-  }
-  return DMIP_OK;
-}
-
-// the tanh chain's answer, as dmip_sampler_supported_precision's
-int flow_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
-  if (precision == DMIP_PREC_F32) return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
-  if (precision == DMIP_PREC_F32X3 || precision == DMIP_PREC_FP16)
-    return dmip::x3_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int dmip_flow_logp_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
-  return dmip::f32_flow_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
-}
-
-int dmip_flow_logp_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
-  return flow_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
-}
-
-int dmip_flow_logp(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
-                   const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
-                   float* latent_out_dev, void* stream) {
-  return flow_logp_impl(mode, net, prior, sde, x_dev, y_dev, n_y, ydim, xdim, n, num_steps, logp_out_dev,
-                        latent_out_dev, DMIP_PREC_F32, stream);
-}
-
-int dmip_flow_logp_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* x_dev,
-                      const float* y_dev, int n_y, int ydim, int xdim, int64_t n, int num_steps, float* logp_out_dev,
-                      float* latent_out_dev, int precision, void* stream) {
-  return flow_logp_impl(mode, net, prior, sde, x_dev, y_dev, n_y, ydim, xdim, n, num_steps, logp_out_dev,
-                        latent_out_dev, precision, stream);
-}
-
-int dmip_flow_sample_supported(int mode, int width, int n_hidden, int xdim, int ydim) {
-  return dmip::f32_flow_sample_supported(mode, width, n_hidden, xdim, ydim) ? 1 : 0;
-}
-
-int dmip_flow_sample_supported_precision(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
-  return flow_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
-}
-
-int dmip_flow_sample(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde, const float* y_dev,
-                     int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset, int num_steps, float mean,
-                     float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev, float* logq_out_dev,
-                     void* stream) {
-  return flow_sample_impl(mode, net, prior, sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv,
-                          seed, x0_dev, x_out_dev, logq_out_dev, DMIP_PREC_F32, stream);
-}
-
-int dmip_flow_sample_ex(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
-                        const float* y_dev, int n_y, int ydim, int xdim, int64_t n_chains, int64_t chain_offset,
-                        int num_steps, float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
-                        float* logq_out_dev, int precision, void* stream) {
-  return flow_sample_impl(mode, net, prior, sde, y_dev, n_y, ydim, xdim, n_chains, chain_offset, num_steps, mean, stdv,
-                          seed, x0_dev, x_out_dev, logq_out_dev, precision, stream);
-}
-
-int dmip_flow_pairs_supported(int precision, int mode, int width, int n_hidden, int xdim, int ydim) {
-  return flow_supported_precision(precision, mode, width, n_hidden, xdim, ydim);
-}
-
-int dmip_flow_logp_pairs(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
-                         const float* x_dev, const float* y_dev, int ydim, int xdim, int64_t n, int num_steps,
-                         float* logp_out_dev, float* latent_out_dev, int precision, void* stream) {
-  return flow_logp_pairs_impl(mode, net, prior, sde, x_dev, y_dev, ydim, xdim, n, num_steps, logp_out_dev,
-                              latent_out_dev, precision, stream);
-}
-
-int dmip_flow_sample_pairs(int mode, const dmip_mlp* net, const dmip_mlp* prior, const dmip_vpsde* sde,
-                           const float* y_dev, int ydim, int xdim, int64_t n, int64_t chain_offset, int num_steps,
-                           float mean, float stdv, uint64_t seed, const float* x0_dev, float* x_out_dev,
-                           float* logq_out_dev, int precision, void* stream) {
-  return flow_sample_pairs_impl(mode, net, prior, sde, y_dev, ydim, xdim, n, chain_offset, num_steps, mean, stdv, seed,
-                                x0_dev, x_out_dev, logq_out_dev, precision, stream);
-}
-
-}  // extern "C"
-
 // ------------------------------------------------------------------- scatterometry surrogate: forward, MH, DPS
 namespace {
 
@@ -1067,8 +633,7 @@ int dmip_mh_sample_ex(const dmip_surrogate* s, const dmip_scat_noise* noise, con
   p.b2 = sp.b2;
   p.lam = sp.lam;
   p.e_out = e_out_dev;
-  p.err = status_word(dmip::stream_device(st));
-  if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+  if (int rc = status_word_or_fail(p.err, st)) return rc;
   hipError_t e = dmip::launch_mh_x3(p, n_y, st);
   return e == hipSuccess ? DMIP_OK : hip_fail(e, "mh_sample (fp32x3) launch");
 }
@@ -1177,8 +742,7 @@ int dmip_dps_sample_ex(const dmip_mlp* prior, const dmip_surrogate* fwd, const d
   p.mode = mode;
   p.seed = seed;
   p.x_out = x_out_dev;
-  p.err = status_word(dmip::stream_device(st));
-  if (!p.err) return fail(DMIP_ERR_ALLOC, "device status word");
+  if (int rc = status_word_or_fail(p.err, st)) return rc;
   hipError_t e = dmip::launch_dps_x3(p, n_y, st);
   return e == hipSuccess ? DMIP_OK : hip_fail(e, "dps_sample (fp32x3) launch");
 }

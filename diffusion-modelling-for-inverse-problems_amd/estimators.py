@@ -97,6 +97,19 @@ def _check_eta(eta):
     return eta
 
 
+MULTISTEP_GRIDS = ("logsnr", "uniform")
+
+
+def _check_grid(grid, t_end, T):
+    """t_end of a few-step sampling call as a float: None is 1e-3 T; 0 < t_end < T."""
+    if grid not in MULTISTEP_GRIDS:
+        raise ValueError(f"grid must be one of {MULTISTEP_GRIDS}, got {grid!r}")
+    t_end = 1e-3 * T if t_end is None else float(t_end)
+    if not 0.0 < t_end < T:
+        raise ValueError(f"t_end must be in (0, T = {T}), got {t_end}")
+    return t_end
+
+
 def _check_solver(solver, lmbd, model, x0=None, noise=None, grid="logsnr", t_end=None, eta=0.0):
     """The effective lmbd of a sampling call. solver="heun" is the second-order sampler of the probability-flow ODE
     (dmip_ode_sample): lmbd left at its default or given as 1.0, CDE and PosteriorDiffusionEstimator only, no noise
@@ -136,19 +149,6 @@ def _check_solver(solver, lmbd, model, x0=None, noise=None, grid="logsnr", t_end
         raise ValueError("x0= needs solver='heun'; the Euler samplers take their start states through the noise= "
                          "argument (slot 0 of the injected normals)")
     return _check_lmbd(lmbd, model)
-
-
-MULTISTEP_GRIDS = ("logsnr", "uniform")
-
-
-def _check_grid(grid, t_end, T):
-    """t_end of a few-step sampling call as a float: None is 1e-3 T; 0 < t_end < T."""
-    if grid not in MULTISTEP_GRIDS:
-        raise ValueError(f"grid must be one of {MULTISTEP_GRIDS}, got {grid!r}")
-    t_end = 1e-3 * T if t_end is None else float(t_end)
-    if not 0.0 < t_end < T:
-        raise ValueError(f"t_end must be in (0, T = {T}), got {t_end}")
-    return t_end
 
 
 def multistep_table(solver, grid, num_steps, beta_min, beta_max, T, t_end=None, eta=0.0):
@@ -276,20 +276,25 @@ def _flow_hint(precision):
 
 
 def _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec,
-                  lmbd=0.0, solver="euler", x0=None, noise=None, table=None, eta=0.0):
-    """The fused CDE / Posterior launch of sample_device: dmip_multistep_sample for "dpm2m" / "ddim" (`table`: their
-    step table on the device; dmip_multistep_sde_sample at eta != 0), dmip_ode_sample for Heun, dmip_em_sample_lmbd for lmbd != 0, else the reverse SDE's own
-    entry point (dmip_em_sample / dmip_em_sample_posterior)."""
+                  lmbd=0.0, solver="euler", x0=None, noise=None, table=None, eta=0.0, snapshot_every=0, snaps=None,
+                  corrector_steps=0, snr=0.16):
+    """The fused launch of sample_device and, with snapshots, of sample_trajectory: dmip_multistep_sample for "dpm2m" /
+    "ddim" (`table`: their step table on the device; dmip_multistep_sde_sample at eta != 0), dmip_ode_sample for Heun,
+    dmip_em_sample_lmbd for lmbd != 0, else the reverse SDE's own entry point: dmip_em_sample_snapshots with snapshots
+    (CDiffE and its corrector included), dmip_em_sample / dmip_em_sample_posterior without."""
     if solver in _lib.TABLE_SOLVERS:
         launch = _lib.multistep_sde_sample if eta != 0.0 else _lib.multistep_sample
         launch(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed, out, x0,
-               precision=prec)
+               snapshot_every, snaps, prec)
     elif solver == "heun":
         _lib.ode_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, "heun",
-                        x0, precision=prec)
+                        x0, snapshot_every, snaps, prec)
     elif lmbd != 0.0:
         _lib.em_sample_lmbd(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, lmbd,
-                            out, noise, precision=prec)
+                            out, noise, snapshot_every, snaps, prec)
+    elif snaps is not None:
+        _lib.em_sample_snapshots(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed,
+                                 snapshot_every, snaps, out, corrector_steps, snr, prec)
     elif mode == _lib.DMIP_SAMPLER_POSTERIOR:
         _lib.em_sample_posterior(prior, net, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec)
     else:
@@ -357,39 +362,23 @@ class BaseClassDiffusionModel:
         if corrector_steps and mode != _lib.DMIP_SAMPLER_CDIFFE:
             raise ValueError("corrector steps: CDiffE only")
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, nets)
-        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
-        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        net, prior = self._handles(nets, dev)
         if prior is not None and (prior.width, prior.n_hidden) != (net.width, net.n_hidden):
             raise ValueError("prior and likelihood networks must have the same hidden layers")
         prec = _fused_precision(precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim,
-                                [h.act for h in handles], solver, eta)
+                                [h.act for h in (net, prior) if h is not None], solver, eta)
         if prec is None:
             raise ValueError("no fused sampler for this network shape / activation")
         snaps = torch.empty(int(num_steps) // int(snapshot_every), ys.shape[0], int(num_samples), self.xdim,
                             device=dev, dtype=torch.float32)
         seed = _draw_seed() if seed is None else seed
-        if solver in _lib.TABLE_SOLVERS:
-            if not 1 <= int(snapshot_every) <= int(num_steps):
-                raise ValueError("snapshot_every must be in [1, num_steps]")
-            table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta)
-            launch = _lib.multistep_sde_sample if eta != 0.0 else _lib.multistep_sample
-            launch(mode, net, prior, ys, num_samples, chain_offset, num_steps, table, mean, std, seed, out, None,
-                   snapshot_every, snaps, prec)
-            return out, snaps
-        if solver == "heun":
-            if not 1 <= int(snapshot_every) <= int(num_steps):
-                raise ValueError("snapshot_every must be in [1, num_steps]")
-            _lib.ode_sample(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out,
-                            "heun", None, snapshot_every, snaps, prec)
-            return out, snaps
-        if lmbd != 0.0:
-            if not 1 <= int(snapshot_every) <= int(num_steps):
-                raise ValueError("snapshot_every must be in [1, num_steps]")
-            _lib.em_sample_lmbd(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, lmbd,
-                                out, None, snapshot_every, snaps, prec)
-            return out, snaps
-        _lib.em_sample_snapshots(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed,
-                                 snapshot_every, snaps, out, corrector_steps, snr, prec)
+        # (the reverse SDE's own entry point, dmip_em_sample_snapshots, makes this check itself; to the others 0 means
+        # no snapshots)
+        if (solver != "euler" or lmbd != 0.0) and not 1 <= int(snapshot_every) <= int(num_steps):
+            raise ValueError("snapshot_every must be in [1, num_steps]")
+        table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta) if solver in _lib.TABLE_SOLVERS else None
+        _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out, prec, lmbd,
+                      solver, None, None, table, eta, snapshot_every, snaps, corrector_steps, snr)
         return out, snaps
 
     def log_prob(self, x, y, num_steps=200, return_latent=False, precision=None):
@@ -402,17 +391,7 @@ class BaseClassDiffusionModel:
         compiled kernel raises ValueError. precision: None is "fp32" (exact f32); "fp32x3" runs the same scheme on
         the split-fp16 engine (dmip_flow_logp_ex; "fp16" / "bf16" run it too: there is no 16-bit kernel) -- a row
         beyond the split's range then raises "fp16 range", as an explicit precision="fp32x3" sampler call does."""
-        nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: log_prob is implemented for CDE and "
-                                                     "PosteriorDiffusionEstimator only"))
-        precision = _flow_precision(precision)
-        layers = [list(n.hidden_layers) for n in nets]
-        widths = set(w for hl in layers for w in hl)
-        if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
-                not _lib.flow_logp_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
-            raise ValueError(f"log_prob: no compiled log-likelihood kernel for hidden layers {layers}, xdim {self.xdim}"
-                             + _flow_hint(precision))
-        if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
-            raise ValueError("log_prob: the log-likelihood kernel computes the tanh chain only")
+        nets, mode, precision = self._flow_nets("log_prob", "flow_logp_supported", precision)
         from . import parallel
         x = torch.as_tensor(x)
         single = x.ndim == 2
@@ -422,8 +401,7 @@ class BaseClassDiffusionModel:
         xs = (xs[None] if single else xs).contiguous()
         if xs.ndim != 3 or xs.shape[0] != ys.shape[0] or xs.shape[2] != self.xdim:
             raise ValueError("x must be (n, xdim) for one y (ydim,), or (n_y, n, xdim) for ys (n_y, ydim)")
-        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
-        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        net, prior = self._handles(nets, dev)
         logp = torch.empty(xs.shape[0], xs.shape[1], device=dev, dtype=torch.float32)
         latent = torch.empty_like(xs) if return_latent else None
         # guarded: the device status word is read after the launch
@@ -448,32 +426,25 @@ class BaseClassDiffusionModel:
         raises ValueError. precision: None is "fp32"; "fp32x3" (and "fp16" / "bf16", which run it) is the split-fp16
         engine (dmip_flow_sample_ex): the x of sample_device(solver="heun", precision="fp32x3") at the same seed, and
         "fp16 range" raised for a chain beyond the split's range."""
-        nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: sample_with_log_prob is implemented for "
-                                                     "CDE and PosteriorDiffusionEstimator only"))
-        precision = _flow_precision(precision)
+        def own_checks():  # (made after the model's and the precision's, before the kernel's: _flow_nets)
+            n_y = torch.as_tensor(y).reshape(-1, self.ydim).shape[0]
+            if x0 is not None:
+                shape = tuple(torch.as_tensor(x0).shape)
+                if shape != (n_y, int(num_samples), self.xdim) and \
+                        not (n_y == 1 and shape == (int(num_samples), self.xdim)):
+                    raise ValueError("x0 must have shape (n_y, num_samples, xdim), or (num_samples, xdim) for one y")
+            if int(num_samples) < 1 or int(num_steps) < 1:
+                raise ValueError("sample_with_log_prob: num_samples and num_steps must be >= 1")
+            if not float(std) > 0.0:
+                raise ValueError(f"sample_with_log_prob: std must be > 0, got {std}")
+
+        nets, mode, precision = self._flow_nets("sample_with_log_prob", "flow_sample_supported", precision,
+                                                own_checks)
         single = torch.as_tensor(y).ndim == 1
-        n_y = torch.as_tensor(y).reshape(-1, self.ydim).shape[0]
-        if x0 is not None:
-            shape = tuple(torch.as_tensor(x0).shape)
-            if shape != (n_y, int(num_samples), self.xdim) and not (n_y == 1 and shape == (int(num_samples), self.xdim)):
-                raise ValueError("x0 must have shape (n_y, num_samples, xdim), or (num_samples, xdim) for one y")
-        if int(num_samples) < 1 or int(num_steps) < 1:
-            raise ValueError("sample_with_log_prob: num_samples and num_steps must be >= 1")
-        if not float(std) > 0.0:
-            raise ValueError(f"sample_with_log_prob: std must be > 0, got {std}")
-        layers = [list(n.hidden_layers) for n in nets]
-        widths = set(w for hl in layers for w in hl)
-        if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
-                not _lib.flow_sample_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
-            raise ValueError(f"sample_with_log_prob: no compiled kernel for hidden layers {layers}, xdim {self.xdim}"
-                             + _flow_hint(precision))
-        if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
-            raise ValueError("sample_with_log_prob: the kernel computes the tanh chain only")
         from . import parallel
         dev, ys, sde, out = self._prepare(y, num_samples, num_steps, nets)
         x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
-        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
-        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        net, prior = self._handles(nets, dev)
         logq = torch.empty(ys.shape[0], int(num_samples), device=dev, dtype=torch.float32)
         seed = _draw_seed() if seed is None else seed
         # guarded: the device status word is read after the launch
@@ -481,21 +452,35 @@ class BaseClassDiffusionModel:
                                                        mean, std, seed, out, logq, x0, precision))
         return (out[0], logq[0]) if single else (out, logq)
 
-    def _pairs_check(self, who, precision):
-        """What log_prob_pairs and sample_with_log_prob_pairs refuse before any device work (their per-y siblings'
-        refusals): (nets, mode, precision)."""
+    # what each flow query's kernel is called in "no compiled <...>" and in the tanh-chain refusal
+    _FLOW_KERNELS = {"flow_logp_supported": ("log-likelihood kernel", "log-likelihood kernel"),
+                     "flow_sample_supported": ("kernel", "kernel"), "flow_pairs_supported": ("paired kernel", "kernel")}
+
+    def _flow_nets(self, who, supported, precision, own_checks=None):
+        """What log_prob, sample_with_log_prob and their paired forms refuse before any device work: a model without
+        an ODE form, an unknown precision, [the caller's own argument checks, where it makes them here,] hidden layers
+        or a precision without a kernel (`supported`: the _lib query's name), an activation chain other than tanh.
+        Returns (nets, mode, precision)."""
         nets, mode = _nets_and_mode(self, ValueError(f"{type(self).__name__}: {who} is implemented for CDE and "
                                                      "PosteriorDiffusionEstimator only"))
         precision = _flow_precision(precision)
+        if own_checks is not None:
+            own_checks()
+        missing, tanh_only = self._FLOW_KERNELS[supported]
         layers = [list(n.hidden_layers) for n in nets]
         widths = set(w for hl in layers for w in hl)
         if len(widths) != 1 or len(set(len(hl) for hl in layers)) != 1 or \
-                not _lib.flow_pairs_supported(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
-            raise ValueError(f"{who}: no compiled paired kernel for hidden layers {layers}, xdim {self.xdim}"
+                not getattr(_lib, supported)(layers[0][0], len(layers[0]), self.xdim, self.ydim, mode, precision):
+            raise ValueError(f"{who}: no compiled {missing} for hidden layers {layers}, xdim {self.xdim}"
                              + _flow_hint(precision))
         if any(n.dmip_act != _lib.DMIP_ACT_TANH_TWICE_FIRST for n in nets):
-            raise ValueError(f"{who}: the kernel computes the tanh chain only")
+            raise ValueError(f"{who}: the {tanh_only} computes the tanh chain only")
         return nets, mode, precision
+
+    def _handles(self, nets, dev):
+        """(net, prior): the handles of _nets_and_mode's networks on `dev`; prior is None but for the Posterior."""
+        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
+        return handles[-1], (handles[0] if len(handles) > 1 else None)
 
     def _pairs_y(self, who, y):
         y = torch.as_tensor(y)
@@ -509,7 +494,7 @@ class BaseClassDiffusionModel:
         log_prob(x[:, None, :], y)[:, 0] computes, in one launch over all rows instead of one workgroup per pair
         (dmip_flow_logp_pairs): y enters through a per-row layer-1 bias. A row's value does not depend on n or on the
         row's position. Single-device: shard by slicing rows. CDE and PosteriorDiffusionEstimator."""
-        nets, mode, precision = self._pairs_check("log_prob_pairs", precision)
+        nets, mode, precision = self._flow_nets("log_prob_pairs", "flow_pairs_supported", precision)
         x, y = torch.as_tensor(x), self._pairs_y("log_prob_pairs", y)
         if x.ndim != 2 or x.shape[1] != self.xdim:
             raise ValueError("log_prob_pairs: x must be (n, xdim)")
@@ -521,8 +506,7 @@ class BaseClassDiffusionModel:
         dev = x.device if x.is_cuda else self._exec_device(y)
         dev, ys, sde, _ = self._prepare(y.to(dev), 0, num_steps, nets)
         xs = x.to(device=dev, dtype=torch.float32).contiguous()
-        handles = [n.dmip_handle(dev, self.xdim) for n in nets]
-        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        net, prior = self._handles(nets, dev)
         logp = torch.empty(xs.shape[0], device=dev, dtype=torch.float32)
         latent = torch.empty_like(xs) if return_latent else None
         # guarded: the device status word is read after the launch
@@ -538,7 +522,7 @@ class BaseClassDiffusionModel:
         sample_with_log_prob(y[i], 1, seed=seed, chain_offset=chain_offset + i); x0 (n, xdim) replaces the starts.
         Shards of a run (rows sliced, chain_offset advanced) are bit-identical to the whole run. Single-device. CDE
         and PosteriorDiffusionEstimator."""
-        nets, mode, precision = self._pairs_check("sample_with_log_prob_pairs", precision)
+        nets, mode, precision = self._flow_nets("sample_with_log_prob_pairs", "flow_pairs_supported", precision)
         y = self._pairs_y("sample_with_log_prob_pairs", y)
         n = int(y.shape[0])
         if x0 is not None and tuple(torch.as_tensor(x0).shape) != (n, self.xdim):
@@ -551,8 +535,7 @@ class BaseClassDiffusionModel:
         dev, ys, sde, _ = self._prepare(y, 0, num_steps, nets)
         if x0 is not None:
             x0 = torch.as_tensor(x0).to(device=dev, dtype=torch.float32).contiguous()
-        handles = [m.dmip_handle(dev, self.xdim) for m in nets]
-        net, prior = handles[-1], (handles[0] if len(handles) > 1 else None)
+        net, prior = self._handles(nets, dev)
         out = torch.empty(n, self.xdim, device=dev, dtype=torch.float32)
         logq = torch.empty(n, device=dev, dtype=torch.float32)
         seed = _draw_seed() if seed is None else seed
@@ -600,8 +583,42 @@ class BaseClassDiffusionModel:
         or "uniform"); x0, seed, chain_offset and precision as for "heun". `eta` != 0 (forward): their stochastic
         variants (dmip_multistep_sde_sample), whose chain draws the Euler sampler's normals, x0 and every step's, from
         the same stream (the x0 draw is consumed when x0= is given, so the step noise is the same either way); noise=
-        is refused."""
-        raise NotImplementedError
+        is refused.
+        This body is CDE's and PosteriorDiffusionEstimator's (`_table_score` is what they word differently); CDiffE and
+        the guided samplers have their own, and any other model raises NotImplementedError."""
+        nets, mode = _nets_and_mode(self, NotImplementedError())
+        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end, eta)
+        eta = float(eta)
+        if noise is not None and mode != _lib.DMIP_SAMPLER_CDE:
+            raise ValueError("noise injection is only implemented for the fused CDE sampler")
+        dev, ys, sde, out = self._prepare(y, num_samples, num_steps, nets)
+        seed = _draw_seed() if seed is None else seed
+        net, prior = self._handles(nets, dev)
+        x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
+        prec = None  # (a prior and a likelihood network of unequal hidden layers have no fused kernel)
+        if prior is None or (prior.width, prior.n_hidden) == (net.width, net.n_hidden):
+            prec = _fused_precision(precision or self.precision, mode, net.width, net.n_hidden, self.xdim, self.ydim,
+                                    [h.act for h in (prior, net) if h is not None], solver, eta)
+        if noise is not None:
+            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(noise.shape) != (int(num_steps) + 1, ys.shape[0], int(num_samples), self.xdim):
+                raise ValueError("noise must have shape (num_steps+1, n_y, num_samples, xdim)")
+            if prec is None:
+                raise ValueError("noise injection needs a fused CDE kernel for this shape")
+        table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta) if solver in _lib.TABLE_SOLVERS else None
+        if prec is not None:
+            return _fused_launch(mode, net, prior, sde, ys, num_samples, chain_offset, num_steps, mean, std, seed, out,
+                                 prec, lmbd, solver, x0, noise, table, eta)
+        if table is not None:
+            return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0, table,
+                                          self._table_score, stochastic=eta != 0.0)
+        base = self.sde.base_sde
+
+        def drift(x, y, tvec):
+            return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
+
+        return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
+                               drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
 
     def _prepare(self, y, num_samples, num_steps, nets):
         dev = self._exec_device(y)
@@ -663,39 +680,9 @@ class CDE(BaseClassDiffusionModel):
         score_net = MLP(xdim + ydim + 1, xdim, hidden_layers, nn.Tanh()).to(device)
         self.sde = sdes.PluginReverseSDE(sdes.VariancePreservingSDE(), score_net, T=1, debias=True)
 
-    def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None,
-                      eta=0.0):
-        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end, eta)
-        eta = float(eta)
-        net = self.sde.a
-        dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [net])
-        handle = net.dmip_handle(dev, self.xdim)
-        seed = _draw_seed() if seed is None else seed
-        x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
-        prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_CDE, handle.width, handle.n_hidden,
-                                self.xdim, self.ydim, [handle.act], solver, eta)
-        if noise is not None:
-            noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(noise.shape) != (int(num_steps) + 1, ys.shape[0], int(num_samples), self.xdim):
-                raise ValueError("noise must have shape (num_steps+1, n_y, num_samples, xdim)")
-        if prec is None:
-            if noise is not None:
-                raise ValueError("noise injection needs a fused CDE kernel for this shape")
-            base = self.sde.base_sde
-
-            def drift(x, y, tvec):
-                return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
-
-            if solver in _lib.TABLE_SOLVERS:
-                return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0,
-                                              self._multistep_table(solver, grid, num_steps, t_end, dev, eta),
-                                              lambda x, y, tvec, g: self.sde.a(x, y, tvec), stochastic=eta != 0.0)
-            return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
-                                   drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
-        table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta) if solver in _lib.TABLE_SOLVERS else None
-        return _fused_launch(_lib.DMIP_SAMPLER_CDE, handle, None, sde, ys, num_samples, chain_offset, num_steps, mean,
-                             std, seed, out, prec, lmbd, solver, x0, noise, table, eta)
+    def _table_score(self, x, y, tvec, g):
+        """_multistep_device_loop's a: the score network's output, as the fused kernel takes it."""
+        return self.sde.a(x, y, tvec)
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         from .training import DeviceTrainStep, _plain_adam, device_step_enabled, device_step_ok, fused_config, \
@@ -897,39 +884,10 @@ class PosteriorDiffusionEstimator(BaseClassDiffusionModel):
         self.sde = sdes.PluginReverseSDE(forward_process, score_net, T=1, debias=True)
         self.loss_fn = PosteriorLoss
 
-    def sample_device(self, y, num_samples, num_steps=200, mean=0, std=1, seed=None, chain_offset=0,
-                      noise=None, precision=None, lmbd=0.0, solver="euler", x0=None, grid="logsnr", t_end=None,
-                      eta=0.0):
-        lmbd = _check_solver(solver, lmbd, self, x0, noise, grid, t_end, eta)
-        eta = float(eta)
-        if noise is not None:
-            raise ValueError("noise injection is only implemented for the fused CDE sampler")
+    def _table_score(self, x, y, tvec, g):
+        """_multistep_device_loop's a = g (likelihood + prior) at the table's g, as the fused kernel forms it."""
         score = self.sde.a
-        dev, ys, sde, out = self._prepare(y, num_samples, num_steps, [score.prior_net, score.likelihood_net])
-        seed = _draw_seed() if seed is None else seed
-        prior = score.prior_net.dmip_handle(dev, self.xdim)
-        lik = score.likelihood_net.dmip_handle(dev, self.xdim)
-        prec = None
-        x0 = _x0_tensor(x0, ys, num_samples, self.xdim, dev)
-        if (prior.width, prior.n_hidden) == (lik.width, lik.n_hidden):
-            prec = _fused_precision(precision or self.precision, _lib.DMIP_SAMPLER_POSTERIOR, lik.width, lik.n_hidden,
-                                    self.xdim, self.ydim, [prior.act, lik.act], solver, eta)
-        table = self._multistep_table(solver, grid, num_steps, t_end, dev, eta) if solver in _lib.TABLE_SOLVERS else None
-        if prec is not None:
-            return _fused_launch(_lib.DMIP_SAMPLER_POSTERIOR, lik, prior, sde, ys, num_samples, chain_offset,
-                                 num_steps, mean, std, seed, out, prec, lmbd, solver, x0, table=table, eta=eta)
-        if table is not None:  # a = g (likelihood + prior) at the table's g, as the fused kernel forms it
-            return _multistep_device_loop(self, ys, int(num_samples), seed, chain_offset, mean, std, x0, table,
-                                          lambda x, y, tvec, g: g * (score.likelihood_net(x, y, tvec) +
-                                                                     score.prior_net(x, tvec)),
-                                          stochastic=eta != 0.0)
-        base = self.sde.base_sde
-
-        def drift(x, y, tvec):
-            return (1. - 0.5 * lmbd) * base.g(tvec, x) * self.sde.a(x, y, tvec) - base.f(tvec, x)
-
-        return _em_device_loop(self, ys, int(num_samples), int(num_steps), mean, std, seed, chain_offset,
-                               drift, self.xdim, self.xdim, lmbd=lmbd, solver=solver, x0=x0)
+        return g * (score.likelihood_net(x, y, tvec) + score.prior_net(x, tvec))
 
     def train_epoch(self, optimizer, loss_fn, epoch_data_loader):
         """models/diffusion.py:204-229. On a HIP device with PosteriorLoss on the scatterometry surrogate,

@@ -154,6 +154,67 @@ static void sampler_refusals() {
           "flow: null net");
   refused(dmip_flow_logp(POST, nullptr, nullptr, &sde, buf, buf, 1, 2, 2, 4, 8, nullptr, nullptr, nullptr), INV,
           null_arg, "flow: null prior / output");
+  // the other flow entry points: each one's sequence mode, num_steps, count, stdv, null argument, precision, two faults
+  // at a time (`fake` stands for a handle where the check under test comes before the handle is read)
+  const dmip_mlp* fake = reinterpret_cast<const dmip_mlp*>(buf);
+  const char* steps1 = "num_steps must be >= 1";
+  const char* stdv0 = "stdv must be > 0";
+  const char* prec_unknown = "unknown precision";
+  auto logp_ex = [&](int mode, const dmip_mlp* net, int steps, int prec) {
+    return dmip_flow_logp_ex(mode, net, nullptr, &sde, buf, buf, 1, 2, 2, 4, steps, buf, nullptr, prec, nullptr);
+  };
+  refused(logp_ex(CDIFFE, nullptr, 0, 7), INV, "flow_logp: CDE and Posterior estimators only",
+          "flow_logp_ex: mode before num_steps");
+  refused(logp_ex(CDE, nullptr, 0, 7), INV, steps1, "flow_logp_ex: num_steps before null net");
+  refused(logp_ex(CDE, nullptr, 8, 7), INV, null_arg, "flow_logp_ex: null net before precision");
+  refused(logp_ex(POST, fake, 8, 7), INV, null_arg, "flow_logp_ex: null prior before precision");
+  refused(logp_ex(CDE, fake, 8, 7), INV, prec_unknown, "flow_logp_ex: precision before the handle");
+  refused(logp_ex(CDE, fake, 8, -1), INV, prec_unknown, "flow_logp_ex: precision < 0");
+  auto smp = [&](bool ex, int mode, const dmip_mlp* net, int steps, int64_t n_chains, float stdv, int prec) {
+    return ex ? dmip_flow_sample_ex(mode, net, nullptr, &sde, buf, 1, 2, 2, n_chains, 0, steps, 0.f, stdv, 1, nullptr,
+                                    buf, buf, prec, nullptr)
+              : dmip_flow_sample(mode, net, nullptr, &sde, buf, 1, 2, 2, n_chains, 0, steps, 0.f, stdv, 1, nullptr, buf,
+                                 buf, nullptr);
+  };
+  for (bool ex : {false, true}) {
+    refused(smp(ex, CDIFFE, nullptr, 0, 4, 1.f, 1), INV, "flow_sample: CDE and Posterior estimators only",
+            "flow_sample: mode before num_steps");
+    refused(smp(ex, CDE, nullptr, 0, 0, 1.f, 1), INV, steps1, "flow_sample: num_steps before n_chains");
+    for (int64_t n : {0, -3})
+      refused(smp(ex, CDE, nullptr, 8, n, 0.f, 1), INV, "n_chains must be >= 1", "flow_sample: n_chains before stdv");
+    for (float s : {0.f, -1.f, std::nanf("")})
+      refused(smp(ex, CDE, nullptr, 8, 4, s, 1), INV, stdv0, "flow_sample: stdv before null net");
+    refused(smp(ex, CDE, nullptr, 8, 4, 1.f, 7), INV, null_arg, "flow_sample: null net before precision");
+    refused(smp(ex, POST, fake, 8, 4, 1.f, 7), INV, null_arg, "flow_sample: null prior before precision");
+  }
+  refused(smp(true, CDE, fake, 8, 4, 1.f, 7), INV, prec_unknown, "flow_sample_ex: precision before the handle");
+  refused(dmip_flow_sample_ex(CDE, fake, nullptr, &sde, buf, 1, 2, 2, 4, 0, 8, 0.f, 1.f, 1, nullptr, buf, nullptr, 1,
+                              nullptr),
+          INV, null_arg, "flow_sample_ex: null logq");
+  const char* n1 = "n must be >= 1";
+  auto logp_pairs = [&](int mode, const dmip_mlp* net, int steps, int64_t n, int prec) {
+    return dmip_flow_logp_pairs(mode, net, nullptr, &sde, buf, buf, 2, 2, n, steps, buf, nullptr, prec, nullptr);
+  };
+  refused(logp_pairs(CDIFFE, nullptr, 0, 2, 1), INV, "flow_logp_pairs: CDE and Posterior estimators only",
+          "flow_logp_pairs: mode before num_steps");
+  refused(logp_pairs(CDE, nullptr, 0, 0, 1), INV, steps1, "flow_logp_pairs: num_steps before n");
+  for (int64_t n : {0, -3}) refused(logp_pairs(CDE, nullptr, 8, n, 7), INV, n1, "flow_logp_pairs: n before null net");
+  refused(logp_pairs(CDE, nullptr, 8, 2, 7), INV, null_arg, "flow_logp_pairs: null net before precision");
+  refused(logp_pairs(POST, fake, 8, 2, 7), INV, null_arg, "flow_logp_pairs: null prior before precision");
+  refused(logp_pairs(CDE, fake, 8, 2, 7), INV, prec_unknown, "flow_logp_pairs: precision before the handle");
+  auto smp_pairs = [&](int mode, const dmip_mlp* net, int steps, int64_t n, float stdv, int prec) {
+    return dmip_flow_sample_pairs(mode, net, nullptr, &sde, buf, 2, 2, n, 0, steps, 0.f, stdv, 1, nullptr, buf, buf,
+                                  prec, nullptr);
+  };
+  refused(smp_pairs(CDIFFE, nullptr, 0, 2, 1.f, 1), INV, "flow_sample_pairs: CDE and Posterior estimators only",
+          "flow_sample_pairs: mode before num_steps");
+  refused(smp_pairs(CDE, nullptr, 0, 0, 1.f, 1), INV, steps1, "flow_sample_pairs: num_steps before n");
+  for (int64_t n : {0, -3}) refused(smp_pairs(CDE, nullptr, 8, n, 0.f, 1), INV, n1, "flow_sample_pairs: n before stdv");
+  for (float s : {0.f, -1.f, std::nanf("")})
+    refused(smp_pairs(CDE, nullptr, 8, 2, s, 1), INV, stdv0, "flow_sample_pairs: stdv before null net");
+  refused(smp_pairs(CDE, nullptr, 8, 2, 1.f, 7), INV, null_arg, "flow_sample_pairs: null net before precision");
+  refused(smp_pairs(POST, fake, 8, 2, 1.f, 7), INV, null_arg, "flow_sample_pairs: null prior before precision");
+  refused(smp_pairs(CDE, fake, 8, 2, 1.f, 7), INV, prec_unknown, "flow_sample_pairs: precision before the handle");
   // MH
   refused(dmip_surrogate_forward(nullptr, buf, 4, buf, nullptr), INV, "null surrogate handle", "surrogate_forward: null");
   refused(dmip_log_posterior(nullptr, &nz_bad, buf, buf, 5, -1, buf, nullptr, nullptr), INV, "null surrogate handle",

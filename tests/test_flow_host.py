@@ -149,6 +149,50 @@ def test_lmbd_and_flow_reject_bad_step_counts(lib, dmip):
         assert b"num_steps" in lib.dmip_last_error()
 
 
+def test_flow_entry_points_refuse_in_their_order(lib, dmip):
+    """dmip_flow_logp_ex, dmip_flow_sample and dmip_flow_sample_ex with no handle, two faults at a time: the earlier
+    check's status and exact message (tests/asan/capi_args.cpp's rows, through ctypes). Each entry point's sequence is
+    mode, num_steps, [n_chains, stdv: the sampling forms only,] null argument, precision; `p` stands for a handle where
+    the check under test comes before the handle is read."""
+    L = dmip._lib
+    sde = ctypes.byref(L.vpsde(0.1, 20.0, 1.0))
+    C, P, X = L.DMIP_SAMPLER_CDE, L.DMIP_SAMPLER_POSTERIOR, L.DMIP_SAMPLER_CDIFFE
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+
+    def logp_ex(mode, net, steps, prec):
+        return lib.dmip_flow_logp_ex(mode, net, None, sde, p, p, 1, 2, 2, 4, steps, p, None, prec, None)
+
+    def smp(ex, mode, net, steps, n_chains, stdv, prec, logq=p):
+        a = (mode, net, None, sde, p, 1, 2, 2, n_chains, 0, steps, 0.0, stdv, 1, None, p, logq)
+        return lib.dmip_flow_sample_ex(*a, prec, None) if ex else lib.dmip_flow_sample(*a, None)
+
+    rows = [
+        (lambda: logp_ex(X, None, 0, 7), "flow_logp: CDE and Posterior estimators only"),
+        (lambda: logp_ex(C, None, 0, 7), "num_steps must be >= 1"),
+        (lambda: logp_ex(C, None, 8, 7), "null argument"),
+        (lambda: logp_ex(P, p, 8, 7), "null argument"),
+        (lambda: logp_ex(C, p, 8, 7), "unknown precision"),
+        (lambda: logp_ex(C, p, 8, -1), "unknown precision"),
+        (lambda: smp(True, C, p, 8, 4, 1.0, 7), "unknown precision"),
+        (lambda: smp(True, C, p, 8, 4, 1.0, 1, logq=None), "null argument"),
+    ]
+    for ex in (False, True):
+        rows += [
+            (lambda ex=ex: smp(ex, X, None, 0, 4, 1.0, 1), "flow_sample: CDE and Posterior estimators only"),
+            (lambda ex=ex: smp(ex, C, None, 0, 0, 1.0, 1), "num_steps must be >= 1"),
+            (lambda ex=ex: smp(ex, C, None, 8, 0, 0.0, 1), "n_chains must be >= 1"),
+            (lambda ex=ex: smp(ex, C, None, 8, -3, 0.0, 1), "n_chains must be >= 1"),
+            (lambda ex=ex: smp(ex, C, None, 8, 4, 0.0, 1), "stdv must be > 0"),
+            (lambda ex=ex: smp(ex, C, None, 8, 4, -1.0, 1), "stdv must be > 0"),
+            (lambda ex=ex: smp(ex, C, None, 8, 4, float("nan"), 1), "stdv must be > 0"),
+            (lambda ex=ex: smp(ex, C, None, 8, 4, 1.0, 7), "null argument"),
+            (lambda ex=ex: smp(ex, P, p, 8, 4, 1.0, 7), "null argument"),
+        ]
+    for i, (call, msg) in enumerate(rows):
+        assert (call(), lib.dmip_last_error().decode()) == (L.DMIP_ERR_INVALID, msg), i
+
+
 def test_flow_logp_supported_shapes(lib, dmip):
     sup = dmip._lib.flow_logp_supported
     P = dmip._lib.DMIP_SAMPLER_POSTERIOR

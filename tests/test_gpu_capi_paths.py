@@ -1,9 +1,11 @@
-"""The host launch path of the C-ABI samplers (csrc/dmip_capi_sample.cpp) with real handles. Needs an MI355X:
-`pytest -m gpu`.
+"""The host launch path of the C-ABI samplers (csrc/dmip_capi_sample.cpp) and of the probability-flow entry points
+(csrc/dmip_capi_flow.cpp) with real handles. Needs an MI355X: `pytest -m gpu`.
 
 (a) Refusals: every sampler, flow, DPS and MH entry point through ctypes with one argument wrong at a time, and two
     at a time where two entry points share a check (the first check's refusal wins). Status and dmip_last_error text
     are literals: sharing a check must not change what a caller is told, or which of two faults it is told first.
+    The eight flow entry points share one implementation; each keeps its own order and wording (FLOW_MORE), checked
+    at the smallest compiled shape, where a valid call launches one tiny grid.
 (b) One small launch (64 chains, 4 steps, 2 ys, fixed seed) through every branch of that path -- each engine's
     per-launch scratch, each layer-1 image, the ring images at width 512, Heun with and without x0, snapshots,
     lmbd = 1, injected noise, log_prob, DPS and MH -- against the oracle at the tolerance the engine's own test file
@@ -70,6 +72,13 @@ SIG = {
     "dmip_ode_sample": "mode net prior sde y n_y ydim xdim n_chains off steps mean stdv seed precision solver x0 every "
                        "snap x_out stream",
     "dmip_flow_logp": "mode net prior sde x y n_y ydim xdim n_chains steps logp latent stream",
+    "dmip_flow_logp_ex": "mode net prior sde x y n_y ydim xdim n_chains steps logp latent precision stream",
+    "dmip_flow_sample": "mode net prior sde y n_y ydim xdim n_chains off steps mean stdv seed x0 x_out logq stream",
+    "dmip_flow_sample_ex": "mode net prior sde y n_y ydim xdim n_chains off steps mean stdv seed x0 x_out logq "
+                           "precision stream",
+    "dmip_flow_logp_pairs": "mode net prior sde x y ydim xdim n_chains steps logp latent precision stream",
+    "dmip_flow_sample_pairs": "mode net prior sde y ydim xdim n_chains off steps mean stdv seed x0 x_out logq precision "
+                              "stream",
     "dmip_dps_sample_ex": "dps_prior sur nz sde y23 n_y n_chains off steps mean stdv seed dps_mode zeta precision "
                           "x_out stream",
     "dmip_mh_sample_ex": "sur nz y23 n_y n_chains off steps noise_std seed x_init inj_noise inj_unif precision x_out "
@@ -77,7 +86,16 @@ SIG = {
 }
 SAMPLERS = ["dmip_em_sample", "dmip_em_sample_posterior", "dmip_em_sample_cdiffe", "dmip_em_sample_snapshots",
             "dmip_em_sample_lmbd", "dmip_ode_sample"]
-WITH_MODE = ["dmip_em_sample_snapshots", "dmip_em_sample_lmbd", "dmip_ode_sample", "dmip_flow_logp"]
+# the flow entry points beside dmip_flow_logp: (who in the messages, what the count is called, rows or chains, per-y,
+# takes a precision, kind in "no compiled <kind>", the SiLU refusal's tail)
+FLOW_MORE = {
+    "dmip_flow_logp_ex": ("flow_logp", None, True, True, True, "log-likelihood kernel", "no SiLU log-likelihood kernel"),
+    "dmip_flow_sample": ("flow_sample", "n_chains", False, True, False, "flow_sample kernel", "no SiLU kernel"),
+    "dmip_flow_sample_ex": ("flow_sample", "n_chains", False, True, True, "flow_sample kernel", "no SiLU kernel"),
+    "dmip_flow_logp_pairs": ("flow_logp_pairs", "n", True, False, True, "paired flow kernel", "no SiLU kernel"),
+    "dmip_flow_sample_pairs": ("flow_sample_pairs", "n", False, False, True, "paired flow kernel", "no SiLU kernel"),
+}
+WITH_MODE = ["dmip_em_sample_snapshots", "dmip_em_sample_lmbd", "dmip_ode_sample", "dmip_flow_logp"] + list(FLOW_MORE)
 
 
 @pytest.fixture(scope="module")
@@ -92,14 +110,21 @@ def env(dmip, golden):
     dps = dmip.DPS(3, 23, [256] * 3)
     pr = importlib.import_module("diffusion-modelling-for-inverse-problems_amd.problems")
     sur_model, _ = _surrogate(golden)
-    keep = [cde, cdiffe, post, post2, dps, sur_model]  # (the handles live as long as their networks)
+    # the smallest compiled shape, for the flow entry points: width 64, 1 hidden layer, xdim 2; a SiLU network of that
+    # shape, and xdim 4, which has no flow kernel
+    cde1, post1, cde_x4 = dmip.CDE(2, 2, [64]), dmip.PosteriorDiffusionEstimator(2, 2, [64]), dmip.CDE(4, 2, [64])
+    silu1 = dmip.MLP(2 + 2 + 1, 2, [64], torch.nn.SiLU()).to(DEV)
     buf = torch.zeros(4096, device=DEV)
+    # (the handles live as long as their networks)
+    keep = [cde, cdiffe, post, post2, dps, sur_model, cde1, post1, cde_x4, silu1, buf]
     h = lambda net, xdim=2: net.dmip_handle(dev, xdim).h
     v = dict(
         cde=h(cde.sde.a), cdiffe=h(cdiffe.sde.a), lik=h(post.sde.a.likelihood_net), prior=h(post.sde.a.prior_net),
         prior_other=h(post2.sde.a.prior_net), dps_prior=h(dps.prior_net, 3), sur=pr.surrogate_handle(sur_model, dev).h,
         sde=L.vpsde(0.1, 20.0, 1.0), sde_t0=L.vpsde(0.1, 20.0, 0.0), nz=L.scat_noise(0.2, 0.01, 1000.0),
-        nz_bad=L.scat_noise(0.2, 0.0, 1000.0), buf=L.ptr(buf), keep=keep)
+        nz_bad=L.scat_noise(0.2, 0.0, 1000.0), buf=L.ptr(buf), keep=keep,
+        cde1=h(cde1.sde.a), lik1=h(post1.sde.a.likelihood_net), prior1=h(post1.sde.a.prior_net), silu1=h(silu1),
+        cde_x4=h(cde_x4.sde.a, 4), out1=L.ptr(buf[1024:]), out2=L.ptr(buf[2048:]), out3=L.ptr(buf[3072:]))
     return L, v
 
 
@@ -114,7 +139,7 @@ def _call(env, entry, **over):
              precision=L.DMIP_PREC_F32, noise=None, x_out=v["buf"], stream=None, corr=0, snr=0.16, every=2,
              snap=v["buf"], lmbd=1.0, solver=L.DMIP_SOLVER_HEUN, x0=None, x=v["buf"], logp=v["buf"], latent=None,
              dps_prior=v["dps_prior"], sur=v["sur"], nz=v["nz"], dps_mode=L.DMIP_DPS_NORM, zeta=0.05, noise_std=0.5,
-             x_init=None, inj_noise=None, inj_unif=None, e_out=None)
+             x_init=None, inj_noise=None, inj_unif=None, e_out=None, logq=v["buf"])
     a.update(over)
     args = [ctypes.byref(a[k]) if k in ("sde", "nz") and a[k] is not None else a[k] for k in SIG[entry].split()]
     lib = L.lib()
@@ -141,7 +166,7 @@ def test_valid_arguments_are_accepted_with_no_chains(env):
     """The argument sets the refusals below start from are valid: with n_chains = 0 every entry point returns OK (and
     launches nothing)."""
     L, _ = env
-    for entry, kw in _each(L, list(SIG)):
+    for entry, kw in _each(L, [e for e in SIG if e not in FLOW_MORE]):
         rc, msg = _call(env, entry, n_chains=0, **kw)
         assert rc == 0, (entry, kw, rc, msg)
 
@@ -243,6 +268,122 @@ def test_sampler_and_flow_refusals_two_faults_keep_their_order(env):
                "prior and likelihood networks must have the same hidden layers")]
     for entry, over, msg in cases:
         rc, got = _call(env, entry, **over)
+        assert got == msg and rc in (INVALID, UNSUPPORTED), (entry, over, rc, got)
+
+
+def _fcall(env, entry, **over):
+    """_call for the flow entry points of FLOW_MORE at their smallest shape: the 1-hidden-layer handles, 8 rows or
+    chains, 2 steps, outputs apart from the inputs."""
+    L, v = env
+    post = over.get("mode", L.DMIP_SAMPLER_CDE) == L.DMIP_SAMPLER_POSTERIOR
+    a = dict(mode=L.DMIP_SAMPLER_CDE, net=v["lik1"] if post else v["cde1"], prior=v["prior1"] if post else None,
+             n_chains=8, steps=2, x_out=v["out1"], logp=v["out2"], logq=v["out2"])
+    a.update(over)
+    return _call(env, entry, **a)
+
+
+def test_flow_entry_points_launch_and_take_no_rows_as_they_do(env):
+    """The argument sets the flow refusals below start from are valid: each entry point launches its tiny grid, in
+    exact f32 and (where it takes a precision) fp32x3, and the device reports nothing. n = 0 is OK for dmip_flow_logp
+    and its _ex form only: the other four refuse it by name."""
+    L, v = env
+    for entry, kw in _each(L, list(FLOW_MORE)):
+        who, count, rows, per_y, has_prec, _, _ = FLOW_MORE[entry]
+        for prec in ([L.DMIP_PREC_F32, L.DMIP_PREC_F32X3] if has_prec else [L.DMIP_PREC_F32]):
+            over = dict(kw, precision=prec, latent=v["out3"])
+            assert _fcall(env, entry, **over)[0] == 0, (entry, over, L.lib().dmip_last_error())
+            L.device_status(torch.device(DEV))
+            rc, msg = _fcall(env, entry, n_chains=0, **over)
+            if count is None:
+                assert rc == 0, (entry, over, msg)
+            else:
+                assert (rc, msg) == (INVALID, f"{count} must be >= 1"), (entry, over)
+
+
+def test_flow_refusals_one_fault(env):
+    """test_sampler_and_flow_refusals_one_fault for the other flow entry points: check_nets' messages with each one's
+    name, rows against chains, the three SiLU wordings, "no compiled ..." with and without the precision."""
+    L, v = env
+    cases = []
+    for entry, kw in _each(L, list(FLOW_MORE)):
+        who, count, rows, per_y, has_prec, kind, silu = FLOW_MORE[entry]
+        cases += [
+            (entry, dict(kw, net=v["prior1"]), INVALID, f"{who} needs an x,y,t network"),
+            (entry, dict(kw, xdim=3), INVALID, "xdim does not match the network"),
+            (entry, dict(kw, ydim=3), INVALID, "ydim does not match the network"),
+            (entry, dict(kw, n_chains=-1), INVALID, "negative row count" if count is None else f"{count} must be >= 1"),
+            (entry, dict(kw, steps=0), INVALID, "num_steps must be >= 1"),
+            (entry, dict(kw, sde=v["sde_t0"]), INVALID, "T must be > 0"),
+            (entry, dict(kw, net=None), INVALID, "null argument"),
+            (entry, dict(kw, sde=None), INVALID, "null argument"),
+            (entry, dict(kw, y=None), INVALID, "null argument"),
+            (entry, dict(kw, **({"logp": None} if rows else {"x_out": None})), INVALID, "null argument"),
+        ]
+        if per_y:
+            cases += [(entry, dict(kw, n_y=n_y), INVALID, "n_y must be in [1, 65535]") for n_y in (0, 65536)]
+        if not rows:
+            cases += [(entry, dict(kw, off=-1), INVALID, "negative chain count/offset"),
+                      (entry, dict(kw, stdv=0.0), INVALID, "stdv must be > 0"),
+                      (entry, dict(kw, logq=None), INVALID, "null argument")]
+        if has_prec:
+            cases += [(entry, dict(kw, precision=7), INVALID, "unknown precision")]
+        if kw["mode"] == L.DMIP_SAMPLER_POSTERIOR:
+            cases += [
+                (entry, dict(kw, prior=v["prior_other"]), UNSUPPORTED,
+                 "prior and likelihood networks must have the same hidden layers"),
+                (entry, dict(kw, prior=v["lik1"]), INVALID, "prior must be an x,t network with out_dim == xdim"),
+                (entry, dict(kw, prior=None), INVALID, "null argument"),
+            ]
+        else:
+            shape = "for width 64, layers 1, xdim 4"
+            cases += [
+                (entry, dict(kw, net=v["silu1"]), UNSUPPORTED, f"{who}: the tanh chain only ({silu})"),
+                (entry, dict(kw, net=v["cde_x4"], xdim=4), UNSUPPORTED, f"no compiled {kind} (mode 0) {shape}"),
+            ]
+            if has_prec:
+                cases += [(entry, dict(kw, net=v["cde_x4"], xdim=4, precision=prec), UNSUPPORTED,
+                           f"no compiled {kind} (mode 0, precision 2) {shape}")
+                          for prec in (L.DMIP_PREC_F32X3, L.DMIP_PREC_FP16)]
+        cases += [(entry, dict(mode=L.DMIP_SAMPLER_CDIFFE), INVALID, f"{who}: CDE and Posterior estimators only")]
+    for entry, over, rc, msg in cases:
+        assert _fcall(env, entry, **over) == (rc, msg), (entry, over)
+
+
+def test_flow_refusals_two_faults_keep_their_order(env):
+    """Pairs of faults down each flow entry point's own sequence: the earlier check refuses. The sampling forms check
+    their count and stdv before the null arguments; dmip_flow_logp[_ex] leaves its count to the networks' check."""
+    L, v = env
+    cases = []
+    for entry, kw in _each(L, list(FLOW_MORE)):
+        who, count, rows, per_y, has_prec, kind, silu = FLOW_MORE[entry]
+        cases += [
+            (entry, dict(kw, mode=L.DMIP_SAMPLER_CDIFFE, steps=0), f"{who}: CDE and Posterior estimators only"),
+            (entry, dict(kw, steps=0, n_chains=0, net=v["prior1"]), "num_steps must be >= 1"),
+            (entry, dict(kw, net=v["prior1"], sde=v["sde_t0"]), f"{who} needs an x,y,t network"),
+            (entry, dict(kw, xdim=3, ydim=3), "xdim does not match the network"),
+            (entry, dict(kw, ydim=3, sde=v["sde_t0"]), "ydim does not match the network"),
+        ]
+        if count is None:
+            cases += [(entry, dict(kw, n_chains=-1, sde=v["sde_t0"]), "negative row count"),
+                      (entry, dict(kw, n_y=0, n_chains=-1), "n_y must be in [1, 65535]")]
+        else:
+            cases += [(entry, dict(kw, n_chains=0, net=None, **({} if rows else {"stdv": 0.0})), f"{count} must be >= 1")]
+        if not rows:
+            cases += [(entry, dict(kw, stdv=0.0, net=None), "stdv must be > 0"),
+                      (entry, dict(kw, off=-1, sde=v["sde_t0"]), "negative chain count/offset")]
+            if per_y:
+                cases += [(entry, dict(kw, n_y=0, off=-1), "n_y must be in [1, 65535]")]
+        if has_prec:
+            cases += [(entry, dict(kw, net=None, precision=7), "null argument"),
+                      (entry, dict(kw, precision=7, net=v["prior1"]), "unknown precision")]
+        if kw["mode"] == L.DMIP_SAMPLER_POSTERIOR:
+            cases += [(entry, dict(kw, prior=v["prior_other"], sde=v["sde_t0"]),
+                       "prior and likelihood networks must have the same hidden layers")]
+        else:
+            cases += [(entry, dict(kw, sde=v["sde_t0"], net=v["silu1"]), "T must be > 0"),
+                      (entry, dict(kw, sde=v["sde_t0"], net=v["cde_x4"], xdim=4), "T must be > 0")]
+    for entry, over, msg in cases:
+        rc, got = _fcall(env, entry, **over)
         assert got == msg and rc in (INVALID, UNSUPPORTED), (entry, over, rc, got)
 
 

@@ -121,6 +121,34 @@ def test_pairs_reject_bad_arguments(lib, dmip):
         assert b"stdv" in lib.dmip_last_error()
 
 
+def test_pairs_refuse_in_their_order(lib, dmip):
+    """Both paired entry points with no handle, two faults at a time: the earlier check's status and exact message
+    (tests/asan/capi_args.cpp's rows, through ctypes). The sequence is mode, num_steps, n, [stdv: the sampling form
+    only,] null argument, precision; `p` stands for a handle where the check under test comes before it is read."""
+    L = dmip._lib
+    sde = L.vpsde(0.1, 20.0, 1.0)
+    C, P, X = L.DMIP_SAMPLER_CDE, L.DMIP_SAMPLER_POSTERIOR, L.DMIP_SAMPLER_CDIFFE
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    rows = []
+    for who, call in (("flow_logp_pairs", _lp), ("flow_sample_pairs", _sp)):
+        rows += [
+            (call, dict(mode=X, net=None, num_steps=0), f"{who}: CDE and Posterior estimators only"),
+            (call, dict(mode=C, net=None, num_steps=0, n=0), "num_steps must be >= 1"),
+            (call, dict(mode=C, net=None, n=0, precision=7), "n must be >= 1"),
+            (call, dict(mode=C, net=None, n=-3, precision=7), "n must be >= 1"),
+            (call, dict(mode=C, net=None, precision=7), "null argument"),
+            (call, dict(mode=P, net=p, precision=7), "null argument"),
+            (call, dict(mode=C, net=p, precision=7), "unknown precision"),
+        ]
+    rows += [(_sp, dict(mode=C, net=None, n=0, std=0.0), "n must be >= 1")]
+    rows += [(_sp, dict(mode=C, net=None, std=s), "stdv must be > 0") for s in (0.0, -1.0, float("nan"))]
+    for call, kw, msg in rows:
+        kw = dict(kw)
+        rc = call(lib, kw.pop("mode"), kw.pop("net"), None, sde, p, p, p, **kw)
+        assert (rc, lib.dmip_last_error().decode()) == (L.DMIP_ERR_INVALID, msg), (call.__name__, kw)
+
+
 # ------------------------------------------------------------------------------------- (c) Python refusals
 def test_python_refusals(lib, dmip):
     """ValueError before any device is looked for: estimators without an ODE form, shapes and activations without a
